@@ -1,6 +1,6 @@
 """Headline benchmark: Mpixels/s forward+backward, 5k-tri mesh, 1024x1024, batch 32.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c4] [--handover u8|f32]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c4] [--handover u8|f32] [--dump-outputs DIR]
 
 With --gpus N > 1 and no WORLD_SIZE in the environment this process only LAUNCHES the N ranks
 (`python -m torch.distributed.run`, fresh children, before anything here has touched a GPU), relays
@@ -213,6 +213,7 @@ def make_step(job, device, gather, handover="f32", spelling="l1_loss", all_gradi
         else:
             loss = mesh_renderer.losses.l1_loss(image, target)   # mean |image - target|, one HIP pass each way
         loss.backward()
+        state["loss"] = loss.detach()   # (detached: the loss node must not outlive its step)
         return loss
 
     def graph_step():   # for mesh_renderer.capture_step: .grad stays the graph's static memory
@@ -283,6 +284,29 @@ def cpu_baseline(batch, width, height, sphere_k, sample_images):
                             "value": round(n_par * px / (fn_ + bn) / 1e6, 3)},
         },
     }
+
+
+DUMP_IMAGE_PIXELS = 1 << 20   # --dump-outputs: RGBA of this many pixels of the image (16 MB), a fixed seeded sample
+
+
+def dump_outputs(out_dir, state, vertices, seed=0):
+    """--dump-outputs: what the LAST timed step handed its caller, as float32 .npy files in out_dir --
+      image_sample   [P,4]   render()'s [B,H,W,4] image at P = DUMP_IMAGE_PIXELS pixels drawn without replacement
+                             from a generator seeded with `seed`, in ascending flat-index order (all pixels if fewer)
+      loss           []      the step's mean |image - target|
+      vertices_grad  [B,V,3] d loss / d vertex positions
+    The job and the target are built without randomness, so two builds given the same arguments compare array for array.
+    (The backward accumulates with float atomics: from run to run vertices_grad agrees to rounding, not bit for bit.)"""
+    import numpy as np
+    image = state["image"].detach()
+    pixels = image.numel() // 4
+    pick = torch.randperm(pixels, generator=torch.Generator().manual_seed(seed))[:DUMP_IMAGE_PIXELS].sort().values
+    arrays = {"image_sample": image.reshape(pixels, 4)[pick.to(image.device)],
+              "loss": state["loss"],
+              "vertices_grad": vertices.grad}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().to(torch.float32).cpu().numpy())
 
 
 LEG_GROUPS_MS = {}   # label -> the three timed groups of a leg (its figure is their median)
@@ -540,7 +564,12 @@ def main():
     ap.add_argument("--extras", type=int, default=1,
                     help="0: skip the legs that run after the timed region (other spellings, gradient sets, configurations)")
     ap.add_argument("--cpu-sample", type=int, default=12, help="images timed for cpu_baseline (0 = skip)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0's image sample, loss and vertex "
+                         "gradients) to DIR/<name>.npy as float32, ~17 MB in all: see dump_outputs")
     args = ap.parse_args()
+    if args.dump_outputs and args.steps < 1:
+        ap.error("--dump-outputs needs at least one timed step (--steps >= 1)")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return spawn_ranks(args)          # before any GPU call: the ranks are fresh processes
@@ -673,6 +702,8 @@ def main():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
     assert vertices.grad is not None and bool(torch.isfinite(vertices.grad).all())
+    if args.dump_outputs and rank == 0:   # (before the N > 1 loops below run more steps)
+        dump_outputs(args.dump_outputs, step_state, vertices)
 
     # N > 1, also outside the timed region: the same loop with the hand-over switched off, so that the
     # first scaling run separates how the rendering scales from what the root's inbound links cost.
