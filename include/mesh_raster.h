@@ -505,6 +505,34 @@ int mr_vertex_normals_backward(const float *dnormals, const float *vertices, con
                                const int32_t *vertex_entries, int B, int V, int T, float *dvertices,
                                void *stream);
 
+/* ---- silhouette antialiasing (no reference counterpart) ----------------------------------
+ * Analytic antialiasing of a hard-rasterized image ("Silhouette antialiasing"): each
+ * horizontal / vertical pair of neighbouring pixels whose ids differ, or of which exactly one is covered
+ * (id != 0 or (b0 + b1) + b2 >= 0.9), is blended by where the front triangle's exit edge crosses the
+ * segment between the two pixel centres, when that edge is a silhouette of the mesh; the crossing point is
+ * differentiated with respect to the edge's clip-space x, y, w.  Decisions in un-fused binary32.
+ *   image     [B,H,W,C] f32, any C >= 1, rows in the rasterizer's order (row 0 = bottom)
+ *   ids, bary, z  [B,H,W] i32, [B,H,W,3] f32, [B,H,W] f32: mr_rasterize_forward's outputs for `clip`
+ *   clip      [B,V,4] f32, 16-byte aligned
+ *   triangles [T,3] i32, shared by the batch
+ *   opposite  [T,3] i32: for the edge opposite corner k of triangle t, the neighbouring triangle's vertex
+ *             across it, -1 for a boundary edge, -2 for a non-manifold or degenerate one
+ *             (mesh_renderer.antialias_topology)
+ *   out       [B,H,W,C] f32 out (may not alias image); image 16-byte aligned when C = 4
+ *   pair_mask [B,H,W] u8 out, optional (NULL = not written): bit k (left, right, down, up) set where the
+ *             pair of this pixel and that neighbour blended and modified THIS pixel
+ * Backward: dout [B,H,W,C] -> dimage [B,H,W,C] (gather form, no atomics) and dclip [B,V,4] (zeroed by the
+ * callee; column z stays 0).  dclip is summed with float atomics, or in 64-bit fixed point under
+ * mr_set_deterministic(1), which needs the workspace. */
+int mr_antialias_forward(const float *image, const int32_t *ids, const float *bary, const float *z,
+                         const float *clip, const int32_t *triangles, const int32_t *opposite, int B, int V,
+                         int T, int W, int H, int C, float *out, uint8_t *pair_mask, void *stream);
+size_t mr_antialias_backward_workspace_bytes(int B, int V, int T, int W, int H, int C);
+int mr_antialias_backward(const float *dout, const float *image, const int32_t *ids, const float *bary,
+                          const float *z, const float *clip, const int32_t *triangles, const int32_t *opposite,
+                          int B, int V, int T, int W, int H, int C, float *dimage, float *dclip, void *workspace,
+                          size_t workspace_bytes, void *stream);
+
 /* ---- clip-space transforms --------------------------------------------------------------
  * perspective(aspect, fov_y, near, far) . look_at(eye, center, up) per image, the product render() and
  * rasterize() apply to the vertices (src/common/camera_utils.py:45-139; src/mesh_renderer/render.py
@@ -550,7 +578,8 @@ int mr_tone_map(const float *image, int B, size_t elements_per_image, float gamm
  * 2^63 after scaling) raises a flag and the outputs of that call are NaN instead of a finite wrong
  * number.  mr_soft_backward is covered as well (fixed-point integer atomics into 64-bit copies of its
  * four vertex outputs, scaled for the 1 / sigma and 1 / gamma its contributions carry; its light
- * gradients are fixed-order sums in either mode).  Not covered, float atomics remain: the composed
+ * gradients are fixed-order sums in either mode).  mr_antialias_backward is covered (fixed-point integer atomics for dclip, scaled from a first pass that finds
+ * its largest per-vertex contribution).  Not covered, float atomics remain: the composed
  * interpolation backward (mr_interpolate_backward, the path for more than 16 attributes).  mr_l1_loss_forward is always deterministic.  Returns the previous setting. */
 int mr_set_deterministic(int on);
 

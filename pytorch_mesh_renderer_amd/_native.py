@@ -16,7 +16,7 @@ _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 # build libmesh_raster_hip_probes.so this way); the product always loads the in-tree library.
 LIB_PATH = os.environ.get("MR_NATIVE_LIB_PATH") or os.path.join(_CSRC, "libmesh_raster_hip.so")
 
-ABI_VERSION = 354
+ABI_VERSION = 355
 GBUFFER_NORMALISED = 1   # mesh_raster.h, MR_GBUFFER_NORMALISED
 TIMER_RASTER_FORWARD, TIMER_SHADE_BACKWARD, TIMER_SHADE_FORWARD, TIMER_RASTER_BACKWARD, TIMER_L1_FORWARD = 0, 1, 2, 3, 4
 MR_OK, MR_EINVAL, MR_EWORKSPACE, MR_ELAUNCH = 0, -1, -2, -3
@@ -32,7 +32,8 @@ _deterministic = False
 
 
 def set_deterministic(on):
-    """Bit-reproducible gradients for the fused render / rasterize backward passes (see
+    """Bit-reproducible gradients for the fused render / rasterize backward passes and the silhouette
+    antialiasing backward (mesh_renderer.antialias) (see
     mr_set_deterministic in include/mesh_raster.h): fixed-point integer accumulation instead of float
     atomics, ~10 % slower.  Process-wide on the Python side: the flag is handed to the library by
     whichever thread launches a backward kernel (autograd runs them on its own thread).  Returns the
@@ -252,6 +253,12 @@ def lib():
         L.mr_vertex_normals_forward.restype = ci
         L.mr_vertex_normals_backward.argtypes = [vp] * 6 + [ci] * 3 + [vp, vp]
         L.mr_vertex_normals_backward.restype = ci
+        L.mr_antialias_forward.argtypes = [vp] * 7 + [ci] * 6 + [vp, vp, vp]
+        L.mr_antialias_forward.restype = ci
+        L.mr_antialias_backward_workspace_bytes.argtypes = [ci] * 6
+        L.mr_antialias_backward_workspace_bytes.restype = sz
+        L.mr_antialias_backward.argtypes = [vp] * 8 + [ci] * 6 + [vp, vp, vp, sz, vp]
+        L.mr_antialias_backward.restype = ci
         _lib = L
     return _lib
 
@@ -685,6 +692,117 @@ def vertex_adjacency(triangles, vertex_count):
     except AttributeError:
         pass
     return offsets, entries
+
+
+def antialias_topology(triangles, vertex_count):
+    """opposite [T,3] i32 on the triangles' device: for the edge opposite corner k of triangle t, the vertex
+    of the neighbouring triangle across it that is not on the edge; -1 for a boundary edge (no neighbour),
+    -2 for a non-manifold edge (three or more triangles share it) or a degenerate one (its two vertices are
+    the same, or the neighbour repeats a vertex of the edge).  Edges are matched by their unordered vertex
+    pair, so winding does not matter.  Torch ops (sort + match): no hot path, and it runs on the CPU too.
+    Cached on the tensor object like vertex_adjacency."""
+    cached = getattr(triangles, "_mr_aa_opposite", None)
+    key = (triangles._version, int(vertex_count), triangles.data_ptr())
+    if cached is not None and cached[0] == key:
+        return cached[1]
+    dev = triangles.device
+    tris = triangles.to(torch.int64).reshape(-1, 3)
+    T = tris.shape[0]
+    # edge k of triangle t joins corners k+1 and k+2; one row per (triangle, edge)
+    a = tris[:, [1, 2, 0]].reshape(-1)
+    b = tris[:, [2, 0, 1]].reshape(-1)
+    c = tris.reshape(-1)                      # the corner opposite the edge
+    lo, hi = torch.minimum(a, b), torch.maximum(a, b)
+    n = 3 * T
+    opposite = torch.full((n,), -1, dtype=torch.int64, device=dev)
+    if n > 0:
+        span = int(vertex_count) + 1
+        ekey = lo * span + hi
+        order = torch.argsort(ekey, stable=True)
+        sk = ekey[order]
+        new_run = torch.ones(n, dtype=torch.bool, device=dev)
+        new_run[1:] = sk[1:] != sk[:-1]
+        run = torch.cumsum(new_run.to(torch.int64), 0) - 1
+        run_size = torch.zeros(n, dtype=torch.int64, device=dev).scatter_add_(0, run, torch.ones_like(run))
+        size = run_size[run]                  # triangles sharing this row's edge (this one included)
+        # a run of two: the partner is the other row of the run
+        first = torch.zeros(n, dtype=torch.int64, device=dev).scatter_reduce_(
+            0, run, torch.arange(n, device=dev), reduce="amin", include_self=False)[run]
+        pos = torch.arange(n, device=dev)
+        partner = torch.where(pos == first, pos + 1, first).clamp(max=n - 1)
+        mate = order[partner]                 # (triangle, edge) row of the neighbour
+        d = c[mate]
+        sorted_opp = torch.where(size == 2, d, torch.full_like(d, -1))
+        sorted_opp = torch.where(size > 2, torch.full_like(d, -2), sorted_opp)
+        # degenerate: an edge with one vertex twice, or a neighbour whose far vertex lies on the edge
+        degenerate = (lo[order] == hi[order]) | ((size == 2) & ((d == lo[order]) | (d == hi[order])))
+        sorted_opp = torch.where(degenerate, torch.full_like(d, -2), sorted_opp)
+        opposite[order] = sorted_opp
+    opposite = opposite.reshape(T, 3).to(torch.int32).contiguous()
+    try:
+        triangles._mr_aa_opposite = (key, opposite)
+    except AttributeError:
+        pass
+    return opposite
+
+
+def _aligned16(t):
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def _chk_antialias(image, ids, bary, z, clip, triangles, opposite):
+    _chk("image", image, _F32, None, None, None, None)
+    B, H, W, C = image.shape
+    if C < 1:
+        raise ValueError("image must have at least one channel, got shape %s" % list(image.shape))
+    _chk("triangle ids", ids, _I32, B, H, W)
+    _chk("barycentrics", bary, _F32, B, H, W, 3)
+    _chk("z", z, _F32, B, H, W)
+    _chk("clip-space vertices", clip, _F32, B, None, 4)
+    _chk("triangles", triangles, _I32, None, 3)
+    _chk("opposite", opposite, _I32, triangles.shape[0], 3)
+    return B, H, W, C
+
+
+def antialias_forward(image, ids, bary, z, clip, triangles, opposite, want_pair_mask=False):
+    """image [B,H,W,C] -> antialiased image [B,H,W,C] (and the pair mask [B,H,W] u8 when asked for:
+    bit k = left, right, down, up pair blended into this pixel)."""
+    B, H, W, C = _chk_antialias(image, ids, bary, z, clip, triangles, opposite)
+    dev = _require_device(image, ids, bary, z, clip, triangles, opposite)
+    L = lib()
+    image, ids, bary, z = _aligned16(image.contiguous()), ids.contiguous(), bary.contiguous(), z.contiguous()
+    clip, triangles, opposite = _aligned16(clip.contiguous()), triangles.contiguous(), opposite.contiguous()
+    V, T = clip.shape[1], triangles.shape[0]
+    out = torch.empty_like(image)
+    mask = torch.empty(B, H, W, dtype=_U8, device=dev) if want_pair_mask else None
+    with torch.cuda.device(dev):
+        rc = L.mr_antialias_forward(_ptr(image), _ptr(ids), _ptr(bary), _ptr(z), _ptr(clip), _ptr(triangles),
+                                    _ptr(opposite), B, V, T, W, H, C, _ptr(out), _ptr(mask), _stream(dev))
+    _check(rc, "mr_antialias_forward")
+    return (out, mask) if want_pair_mask else out
+
+
+def antialias_backward(dout, image, ids, bary, z, clip, triangles, opposite):
+    """-> (dimage [B,H,W,C], dclip [B,V,4])."""
+    B, H, W, C = _chk_antialias(image, ids, bary, z, clip, triangles, opposite)
+    _chk("upstream gradient", dout, _F32, B, H, W, C)
+    dev = _require_device(dout, image, ids, bary, z, clip, triangles, opposite)
+    L = lib()
+    dout, image = _aligned16(dout.contiguous()), image.contiguous()
+    ids, bary, z = ids.contiguous(), bary.contiguous(), z.contiguous()
+    clip, triangles, opposite = _aligned16(clip.contiguous()), triangles.contiguous(), opposite.contiguous()
+    V, T = clip.shape[1], triangles.shape[0]
+    dimage = torch.empty_like(dout)
+    dclip = torch.empty(B, V, 4, dtype=_F32, device=dev)
+    with torch.cuda.device(dev):
+        need = L.mr_antialias_backward_workspace_bytes(B, V, T, W, H, C)
+        ws, have = _workspace(dev, need)
+        _sync_deterministic()
+        rc = L.mr_antialias_backward(_ptr(dout), _ptr(image), _ptr(ids), _ptr(bary), _ptr(z), _ptr(clip),
+                                     _ptr(triangles), _ptr(opposite), B, V, T, W, H, C, _ptr(dimage),
+                                     _ptr(dclip), _ptr(ws), have, _stream(dev))
+    _check(rc, "mr_antialias_backward")
+    return dimage, dclip
 
 
 def shade_backward(drgba, ids, bary, clip, normals, positions, diffuse, triangles, light_positions,

@@ -33,7 +33,7 @@ const char *volatile g_last_accumulate_kernel = "";
 
 extern "C" {
 
-int mr_version(void) { return 354; /* + mr_rasterize_specular_norms_forward, norms2_given; 353: mr_shade_specular_backward_l1 (352: dclip optional, backward_prepared / prepared, mr_debug_soft_nearest, two's-complement sign codes) */ }
+int mr_version(void) { return 355; /* + mr_antialias_forward / _backward; 354: + mr_rasterize_specular_norms_forward, norms2_given; 353: mr_shade_specular_backward_l1 (352: dclip optional, backward_prepared / prepared, mr_debug_soft_nearest, two's-complement sign codes) */ }
 
 int mr_last_hip_error(void) { return mr::g_last_hip_error; }
 
@@ -625,6 +625,46 @@ int mr_vertex_normals_backward(const float *dnormals, const float *vertices, con
     return MR_EINVAL;
   return mr::launch_vertex_normals_backward(dnormals, vertices, sums, triangles, vertex_offsets,
                                             vertex_entries, B, V, dvertices, (hipStream_t)stream);
+}
+
+inline bool bad_antialias_dims(int B, int V, int T, int W, int H, int C) {
+  return bad_dims(B, V, T, W, H) || C < 1 || (size_t)B * V >= (size_t)INT_MAX ||
+         (size_t)B * W * H * C >= ((size_t)1 << 40);
+}
+
+int mr_antialias_forward(const float *image, const int32_t *ids, const float *bary, const float *z,
+                         const float *clip, const int32_t *triangles, const int32_t *opposite, int B, int V,
+                         int T, int W, int H, int C, float *out, uint8_t *pair_mask, void *stream) {
+  if (bad_antialias_dims(B, V, T, W, H, C)) return MR_EINVAL;
+  if (B == 0) return MR_OK;
+  if (!image || !ids || !bary || !z || !out || (V > 0 && !clip) || (T > 0 && (!triangles || !opposite)))
+    return MR_EINVAL;
+  if (image == out || ((uintptr_t)clip & 15u) != 0) return MR_EINVAL;
+  if (C == 4 && (((uintptr_t)image | (uintptr_t)out) & 15u) != 0) return MR_EINVAL;
+  return mr::launch_antialias_forward(image, ids, bary, z, clip, triangles, opposite, B, V, T, W, H, C, out,
+                                      pair_mask, (hipStream_t)stream);
+}
+
+size_t mr_antialias_backward_workspace_bytes(int B, int V, int T, int W, int H, int C) {
+  if (bad_antialias_dims(B, V, T, W, H, C)) return 0;
+  return mr::antialias_backward_ws(B, V);
+}
+
+int mr_antialias_backward(const float *dout, const float *image, const int32_t *ids, const float *bary,
+                          const float *z, const float *clip, const int32_t *triangles, const int32_t *opposite,
+                          int B, int V, int T, int W, int H, int C, float *dimage, float *dclip, void *workspace,
+                          size_t workspace_bytes, void *stream) {
+  if (bad_antialias_dims(B, V, T, W, H, C)) return MR_EINVAL;
+  if (B == 0) return MR_OK;
+  if (!dout || !image || !ids || !bary || !z || !dimage || (V > 0 && (!clip || !dclip)) ||
+      (T > 0 && (!triangles || !opposite)))
+    return MR_EINVAL;
+  if (dimage == dout || ((uintptr_t)clip & 15u) != 0) return MR_EINVAL;
+  if (C == 4 && (((uintptr_t)dout | (uintptr_t)dimage) & 15u) != 0) return MR_EINVAL;
+  const int rc = check_ws(workspace, workspace_bytes, mr::antialias_backward_ws(B, V));
+  if (rc != MR_OK) return rc;
+  return mr::launch_antialias_backward(dout, image, ids, bary, z, clip, triangles, opposite, B, V, T, W, H, C,
+                                       dimage, dclip, workspace, (hipStream_t)stream);
 }
 
 int mr_tone_map(const float *image, int B, size_t elements_per_image, float gamma, int32_t *max_scratch,

@@ -230,6 +230,15 @@ int launch_camera_transforms_backward(const float *dtransforms, const float *eye
                                       float *dup, hipStream_t s);
 int launch_tone_map(const float *image, int B, size_t per_image, float gamma, int *max_bits, float *out,
                     uint8_t *out_u8, hipStream_t s);
+// silhouette antialiasing (antialias.hip)
+size_t antialias_backward_ws(int B, int V);
+int launch_antialias_forward(const float *image, const int32_t *ids, const float *bary, const float *z,
+                             const float *clip, const int32_t *tris, const int32_t *opp, int B, int V, int T, int W,
+                             int H, int C, float *out, uint8_t *pair_mask, hipStream_t s);
+int launch_antialias_backward(const float *dout, const float *image, const int32_t *ids, const float *bary,
+                              const float *z, const float *clip, const int32_t *tris, const int32_t *opp, int B,
+                              int V, int T, int W, int H, int C, float *dimage, float *dclip, void *ws,
+                              hipStream_t s);
 int soft_max_lights();
 int launch_debug_soft_nearest(const float *p, const float *a, const float *b, int n, float *out, hipStream_t s);
 size_t soft_ws(int B, int V, int T, int W, int H);

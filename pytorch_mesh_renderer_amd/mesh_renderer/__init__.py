@@ -1,6 +1,7 @@
 """Same export surface as the reference's src/mesh_renderer/__init__.py:1-5."""
 from .render import render, tone_mapper, tone_mapper_uint8, to_uint8
 from .rasterize import rasterize
+from .antialiasing import antialias, antialias_topology
 from . import losses
 from .graphs import capture_step, CapturedStep
 

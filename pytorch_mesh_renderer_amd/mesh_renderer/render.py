@@ -46,7 +46,7 @@ def _per_batch_vec3(value, batch_size, name):
 def render(vertices, triangles, normals, diffuse_colors, camera_position, camera_lookat,
            camera_up, light_positions, light_intensities, image_width, image_height,
            specular_colors=None, shininess_coefficients=None, ambient_color=None,
-           fov_y=40.0, near_clip=0.01, far_clip=10.0):
+           fov_y=40.0, near_clip=0.01, far_clip=10.0, antialias=False):
     """Render a batch of scenes with Phong shading; returns [B, H, W, 4] RGBA.
 
     Arguments are those of the reference's render() (src/mesh_renderer/render.py
@@ -54,6 +54,11 @@ def render(vertices, triangles, normals, diffuse_colors, camera_position, camera
     (clockwise winding faces the viewer), camera_* [B,3] or [3], lights [B,L,3],
     optional specular_colors [B,V,3] with shininess_coefficients (float, 0-D,
     [B] or [B,V]), optional ambient_color [B,3], fov_y in degrees.
+
+    antialias=True (not in the reference) antialiases the silhouettes with mesh_renderer.antialias
+    before the flip, so that alpha and colour vary continuously with the outline's position and a loss
+    on the outline has a gradient to the vertices; it takes the composed path (rasterizer,
+    interpolation, torch Phong, antialias), not the fused kernels.
     """
     if len(vertices.shape) != 3 or vertices.shape[-1] != 3:
         raise ValueError("Vertices must have shape [batch_size, vertex_count, 3].")
@@ -83,7 +88,7 @@ def render(vertices, triangles, normals, diffuse_colors, camera_position, camera
     if shininess_coefficients is not None and specular_colors is None:
         raise ValueError("Shininess coefficients were supplied without specular colors.")
 
-    if _fused_path_applies(vertices, normals, diffuse_colors, light_positions, specular_colors is not None):
+    if not antialias and _fused_path_applies(vertices, normals, diffuse_colors, light_positions, specular_colors is not None):
         if specular_colors is None:
             return _render_fused(vertices, triangles, normals, diffuse_colors, camera_position,
                                  camera_lookat, camera_up, light_positions, light_intensities,
@@ -119,8 +124,16 @@ def render(vertices, triangles, normals, diffuse_colors, camera_position, camera
 
     # background -1 marks uncovered pixels: a real diffuse colour is never negative
     background = torch.full((vertex_attributes.shape[2],), -1.0, device=device)
-    pixel_attributes = rasterize(vertices, vertex_attributes, triangles, clip_space_transforms,
-                                 image_width, image_height, background)
+    if antialias:
+        # the composed ops of rasterize_clip_space's USE_FUSED_BACKWARD = False branch, kept so that the
+        # G-buffer can be handed on to the antialiasing pass
+        from .rasterize_triangles_ext import AttributeInterpolator, BarycentricRasterizer
+        clip = camera_utils.transform_homogeneous(clip_space_transforms, vertices)
+        ids, bary, z = BarycentricRasterizer.apply(clip, triangles, image_width, image_height)
+        pixel_attributes = AttributeInterpolator.apply(ids, bary, vertex_attributes, triangles, background)
+    else:
+        pixel_attributes = rasterize(vertices, vertex_attributes, triangles, clip_space_transforms,
+                                     image_width, image_height, background)
 
     pixel_normals = torch.nn.functional.normalize(pixel_attributes[..., 0:3], p=2, dim=3)
     pixel_positions = pixel_attributes[..., 3:6]
@@ -134,7 +147,8 @@ def render(vertices, triangles, normals, diffuse_colors, camera_position, camera
             shininess_coefficients = shininess_coefficients.to(device).reshape(-1, 1, 1)
     pixel_mask = (pixel_diffuse >= 0.0).any(dim=3).to(torch.float32)
 
-    return phong_shader(
+    shade = _phong_rgba if antialias else phong_shader
+    image = shade(
         normals=pixel_normals, alphas=pixel_mask, pixel_positions=pixel_positions,
         light_positions=light_positions.to(device),
         light_intensities=light_intensities.to(device),
@@ -142,6 +156,11 @@ def render(vertices, triangles, normals, diffuse_colors, camera_position, camera
         camera_position=camera_position.to(device) if pixel_specular is not None else None,
         specular_colors=pixel_specular, shininess_coefficients=shininess_coefficients,
         ambient_color=ambient_color.to(device) if ambient_color is not None else None)
+    if not antialias:
+        return image
+    from .antialiasing import antialias as antialias_op
+    image = antialias_op(image, clip, triangles, ids, bary, z)
+    return torch.flip(image, dims=[1])
 
 
 def _fused_path_applies(vertices, normals, diffuse_colors, light_positions, specular):
@@ -229,6 +248,15 @@ def phong_shader(normals, alphas, pixel_positions, light_positions, light_intens
     alphas [B,H,W], lights [B,L,3], camera_position [B,3] (enables the specular
     term), shininess broadcastable to [B,H,W], ambient_color [B,3].
     """
+    return torch.flip(_phong_rgba(normals, alphas, pixel_positions, light_positions, light_intensities,
+                                  diffuse_colors, camera_position, specular_colors, shininess_coefficients,
+                                  ambient_color), dims=[1])
+
+
+def _phong_rgba(normals, alphas, pixel_positions, light_positions, light_intensities,
+                diffuse_colors=None, camera_position=None, specular_colors=None,
+                shininess_coefficients=None, ambient_color=None):
+    """phong_shader without its final flip: rows in the rasterizer's order (row 0 = bottom)."""
     batch_size, image_height, image_width = normals.shape[:-1]
     pixel_count = image_height * image_width
     normals = normals.reshape(batch_size, pixel_count, 3)
@@ -266,7 +294,7 @@ def phong_shader(normals, alphas, pixel_positions, light_positions, light_intens
     rgb = rgb.reshape(batch_size, image_height, image_width, 3)
     alpha = alphas.reshape(batch_size, image_height, image_width, 1)
     rgb = torch.where(alpha > 0.5, rgb, torch.zeros_like(rgb))
-    return torch.flip(torch.cat([rgb, alpha], dim=3), dims=[1])
+    return torch.cat([rgb, alpha], dim=3)
 
 
 def tone_mapper(image, gamma):
