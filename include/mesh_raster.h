@@ -533,6 +533,30 @@ int mr_antialias_backward(const float *dout, const float *image, const int32_t *
                           int B, int V, int T, int W, int H, int C, float *dimage, float *dclip, void *workspace,
                           size_t workspace_bytes, void *stream);
 
+/* ---- spherical-harmonics lighting (no reference counterpart) ------------------------------
+ * Diffuse shading of a pixel buffer under second-order SH irradiance ("Spherical-harmonics
+ * lighting"): n = N / max(|N|, 1e-12), E_c = sum_k sh[b,k,c] Y_k(n) with no clamp, rgb = diffuse * E, rgb = 0
+ * where alpha <= 0.5, RGBA out.
+ *   normals, diffuse  pixel i of the batch at normals + i * pixel_stride, diffuse + i * pixel_stride (3 floats
+ *             each): two [B,H,W,3] buffers (pixel_stride 3) or two channel slices of one [B,H,W,C] buffer
+ *             (pixel_stride C >= 3), pixels in the rasterizer's order
+ *   alphas    [B,H,W] f32, or NULL: alpha = 1 where any diffuse channel is >= 0, else 0 (background = -1)
+ *   sh        [B,9,3] f32: world-space irradiance coefficients, basis k, channel c
+ *   flip      nonzero: output row H-1-y holds input row y (row 0 = top, as render()); zero: the same row order
+ *   rgba      [B,H,W,4] f32 out, 16-byte aligned
+ * B <= 65535 and W * H <= 2^30.
+ * Backward: drgba [B,H,W,4] (16-byte aligned, rows as rgba) -> dnormals, ddiffuse (pixel_stride as the inputs),
+ * dalphas [B,H,W] (the alpha channel of drgba; only with alphas) and dsh [B,9,3].  Each of the four may be NULL
+ * (not wanted).  Gather form, no atomics: every pixel writes its own gradients (zeros where masked); dsh is summed
+ * per workgroup into the workspace (needed only with dsh) and then in a fixed order, so it is bit-reproducible. */
+int mr_sh_shade_forward(const float *normals, const float *diffuse, int pixel_stride, const float *alphas,
+                        const float *sh, int B, int W, int H, int flip, float *rgba, void *stream);
+size_t mr_sh_shade_backward_workspace_bytes(int B, int W, int H);
+int mr_sh_shade_backward(const float *drgba, const float *normals, const float *diffuse, int pixel_stride,
+                         const float *alphas, const float *sh, int B, int W, int H, int flip, float *dnormals,
+                         float *ddiffuse, float *dalphas, float *dsh, void *workspace, size_t workspace_bytes,
+                         void *stream);
+
 /* ---- clip-space transforms --------------------------------------------------------------
  * perspective(aspect, fov_y, near, far) . look_at(eye, center, up) per image, the product render() and
  * rasterize() apply to the vertices (src/common/camera_utils.py:45-139; src/mesh_renderer/render.py
@@ -579,7 +603,7 @@ int mr_tone_map(const float *image, int B, size_t elements_per_image, float gamm
  * number.  mr_soft_backward is covered as well (fixed-point integer atomics into 64-bit copies of its
  * four vertex outputs, scaled for the 1 / sigma and 1 / gamma its contributions carry; its light
  * gradients are fixed-order sums in either mode).  mr_antialias_backward is covered (fixed-point integer atomics for dclip, scaled from a first pass that finds
- * its largest per-vertex contribution).  Not covered, float atomics remain: the composed
+ * its largest per-vertex contribution).  mr_sh_shade_backward has no atomics and is bit-reproducible in either mode.  Not covered, float atomics remain: the composed
  * interpolation backward (mr_interpolate_backward, the path for more than 16 attributes).  mr_l1_loss_forward is always deterministic.  Returns the previous setting. */
 int mr_set_deterministic(int on);
 

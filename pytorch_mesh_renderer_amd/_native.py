@@ -16,7 +16,7 @@ _CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 # build libmesh_raster_hip_probes.so this way); the product always loads the in-tree library.
 LIB_PATH = os.environ.get("MR_NATIVE_LIB_PATH") or os.path.join(_CSRC, "libmesh_raster_hip.so")
 
-ABI_VERSION = 355
+ABI_VERSION = 356
 GBUFFER_NORMALISED = 1   # mesh_raster.h, MR_GBUFFER_NORMALISED
 TIMER_RASTER_FORWARD, TIMER_SHADE_BACKWARD, TIMER_SHADE_FORWARD, TIMER_RASTER_BACKWARD, TIMER_L1_FORWARD = 0, 1, 2, 3, 4
 MR_OK, MR_EINVAL, MR_EWORKSPACE, MR_ELAUNCH = 0, -1, -2, -3
@@ -259,6 +259,12 @@ def lib():
         L.mr_antialias_backward_workspace_bytes.restype = sz
         L.mr_antialias_backward.argtypes = [vp] * 8 + [ci] * 6 + [vp, vp, vp, sz, vp]
         L.mr_antialias_backward.restype = ci
+        L.mr_sh_shade_forward.argtypes = [vp, vp, ci, vp, vp, ci, ci, ci, ci, vp, vp]
+        L.mr_sh_shade_forward.restype = ci
+        L.mr_sh_shade_backward_workspace_bytes.argtypes = [ci] * 3
+        L.mr_sh_shade_backward_workspace_bytes.restype = sz
+        L.mr_sh_shade_backward.argtypes = [vp, vp, vp, ci, vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, sz, vp]
+        L.mr_sh_shade_backward.restype = ci
         _lib = L
     return _lib
 
@@ -803,6 +809,104 @@ def antialias_backward(dout, image, ids, bary, z, clip, triangles, opposite):
                                      _ptr(dclip), _ptr(ws), have, _stream(dev))
     _check(rc, "mr_antialias_backward")
     return dimage, dclip
+
+
+def _pixel_stride(normals, diffuse):
+    """The pixel stride C when normals and diffuse are two disjoint three-channel slices of one contiguous
+    [B,H,W,C] buffer (rasterize()'s packed attributes), else None.  Returns (C, normals' channel, diffuse's
+    channel)."""
+    B, H, W, _ = normals.shape
+    if normals.untyped_storage().data_ptr() != diffuse.untyped_storage().data_ptr():
+        return None
+    C = normals.stride(2)
+    for t in (normals, diffuse):
+        want = (H * W * C, W * C, C, 1)
+        if any(n > 1 and st != w for n, st, w in zip(t.shape, t.stride(), want)):
+            return None
+    on, od = normals.storage_offset(), diffuse.storage_offset()
+    cn, cd = on % C, od % C
+    if C < 6 or on - cn != od - cd or cn + 3 > C or cd + 3 > C or abs(cn - cd) < 3:
+        return None
+    return C, cn, cd
+
+
+def _chk_sh(normals, diffuse, alphas, sh):
+    _chk("normals", normals, _F32, None, None, None, 3)
+    B, H, W, _ = normals.shape
+    _chk("diffuse colors", diffuse, _F32, B, H, W, 3)
+    if alphas is not None:
+        _chk("alphas", alphas, _F32, B, H, W)
+    _chk("sh coefficients", sh, _F32, B, 9, 3)
+    if B > 65535 or H * W > 1 << 30:
+        raise ValueError("spherical-harmonics shading takes at most 65535 images of at most 2^30 pixels, got %s"
+                         % list(normals.shape))
+    return B, H, W
+
+
+def _sh_inputs(normals, diffuse, alphas, sh):
+    """-> (normals, diffuse, pixel stride, packed channels or None, alphas, sh) as the kernels read them: a packed
+    pair goes through as it is, anything else is made contiguous."""
+    packed = _pixel_stride(normals, diffuse)
+    if packed is None:
+        normals, diffuse, stride = normals.contiguous(), diffuse.contiguous(), 3
+    else:
+        stride = packed[0]
+    alphas = alphas.contiguous() if alphas is not None else None
+    return normals, diffuse, stride, packed, alphas, sh.contiguous()
+
+
+def sh_shade_forward(normals, diffuse, alphas, sh, flip=True):
+    """normals, diffuse [B,H,W,3] f32 (two channel slices of one contiguous [B,H,W,C] buffer are read in place),
+    alphas [B,H,W] f32 or None (alpha = any(diffuse >= 0)), sh [B,9,3] f32 -> RGBA [B,H,W,4], rows flipped when
+    `flip` (INTEGRATION.md, "Spherical-harmonics lighting")."""
+    B, H, W = _chk_sh(normals, diffuse, alphas, sh)
+    dev = _require_device(*[t for t in (normals, diffuse, alphas, sh) if t is not None])
+    L = lib()
+    normals, diffuse, stride, _, alphas, sh = _sh_inputs(normals, diffuse, alphas, sh)
+    rgba = torch.empty(B, H, W, 4, dtype=_F32, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.mr_sh_shade_forward(_ptr(normals), _ptr(diffuse), stride, _ptr(alphas), _ptr(sh), B, W, H,
+                                   1 if flip else 0, _ptr(rgba), _stream(dev))
+    _check(rc, "mr_sh_shade_forward")
+    return rgba
+
+
+def sh_shade_backward(drgba, normals, diffuse, alphas, sh, flip=True, want_normals=True, want_diffuse=True,
+                      want_alphas=True, want_sh=True, packed_grad=False):
+    """-> (dnormals, ddiffuse, dalphas, dsh); an unwanted gradient is None, and so is dalphas when alphas is None.
+    When normals and diffuse are read in place from one [B,H,W,C] buffer, dnormals and ddiffuse are the same
+    channel slices of one [B,H,W,C] gradient (its other channels zero); with packed_grad=True that buffer is
+    returned in their place: (dpacked, dalphas, dsh)."""
+    B, H, W = _chk_sh(normals, diffuse, alphas, sh)
+    _chk("upstream gradient", drgba, _F32, B, H, W, 4)
+    dev = _require_device(*[t for t in (drgba, normals, diffuse, alphas, sh) if t is not None])
+    L = lib()
+    normals, diffuse, stride, packed, alphas, sh = _sh_inputs(normals, diffuse, alphas, sh)
+    drgba = _aligned16(drgba.contiguous())
+    want_alphas = want_alphas and alphas is not None
+    dpacked = None
+    if packed is not None and (want_normals or want_diffuse or packed_grad):
+        C, cn, cd = packed
+        covered = C == 6 and want_normals and want_diffuse
+        dpacked = (torch.empty if covered else torch.zeros)(B, H, W, C, dtype=_F32, device=dev)
+        dnormals = dpacked[..., cn:cn + 3] if want_normals else None
+        ddiffuse = dpacked[..., cd:cd + 3] if want_diffuse else None
+    else:
+        dnormals = torch.empty(B, H, W, 3, dtype=_F32, device=dev) if want_normals else None
+        ddiffuse = torch.empty(B, H, W, 3, dtype=_F32, device=dev) if want_diffuse else None
+    dalphas = torch.empty(B, H, W, dtype=_F32, device=dev) if want_alphas else None
+    dsh = torch.empty(B, 9, 3, dtype=_F32, device=dev) if want_sh else None
+    with torch.cuda.device(dev):
+        ws, have = None, 0
+        if want_sh:
+            ws, have = _workspace(dev, L.mr_sh_shade_backward_workspace_bytes(B, W, H))
+        rc = L.mr_sh_shade_backward(_ptr(drgba), _ptr(normals), _ptr(diffuse), stride, _ptr(alphas), _ptr(sh), B, W,
+                                    H, 1 if flip else 0, _ptr(dnormals), _ptr(ddiffuse), _ptr(dalphas), _ptr(dsh),
+                                    _ptr(ws), have, _stream(dev))
+    _check(rc, "mr_sh_shade_backward")
+    if packed_grad and dpacked is not None:
+        return dpacked, dalphas, dsh
+    return dnormals, ddiffuse, dalphas, dsh
 
 
 def shade_backward(drgba, ids, bary, clip, normals, positions, diffuse, triangles, light_positions,

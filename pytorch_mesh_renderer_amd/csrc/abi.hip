@@ -33,7 +33,7 @@ const char *volatile g_last_accumulate_kernel = "";
 
 extern "C" {
 
-int mr_version(void) { return 355; /* + mr_antialias_forward / _backward; 354: + mr_rasterize_specular_norms_forward, norms2_given; 353: mr_shade_specular_backward_l1 (352: dclip optional, backward_prepared / prepared, mr_debug_soft_nearest, two's-complement sign codes) */ }
+int mr_version(void) { return 356; /* + mr_sh_shade_forward / _backward; 355: + mr_antialias_forward / _backward; 354: + mr_rasterize_specular_norms_forward, norms2_given; 353: mr_shade_specular_backward_l1 (352: dclip optional, backward_prepared / prepared, mr_debug_soft_nearest, two's-complement sign codes) */ }
 
 int mr_last_hip_error(void) { return mr::g_last_hip_error; }
 
@@ -665,6 +665,40 @@ int mr_antialias_backward(const float *dout, const float *image, const int32_t *
   if (rc != MR_OK) return rc;
   return mr::launch_antialias_backward(dout, image, ids, bary, z, clip, triangles, opposite, B, V, T, W, H, C,
                                        dimage, dclip, workspace, (hipStream_t)stream);
+}
+
+inline bool bad_sh_dims(int B, int W, int H, int pixel_stride) {
+  return B < 0 || B > 65535 || W < 1 || H < 1 || (size_t)W * H > ((size_t)1 << 30) || pixel_stride < 3;
+}
+
+int mr_sh_shade_forward(const float *normals, const float *diffuse, int pixel_stride, const float *alphas,
+                        const float *sh, int B, int W, int H, int flip, float *rgba, void *stream) {
+  if (bad_sh_dims(B, W, H, pixel_stride)) return MR_EINVAL;
+  if (B == 0) return MR_OK;
+  if (!normals || !diffuse || !sh || !rgba || ((uintptr_t)rgba & 15u) != 0) return MR_EINVAL;
+  return mr::launch_sh_shade_forward(normals, diffuse, pixel_stride, alphas, sh, B, W, H, flip != 0, rgba,
+                                     (hipStream_t)stream);
+}
+
+size_t mr_sh_shade_backward_workspace_bytes(int B, int W, int H) {
+  if (bad_sh_dims(B, W, H, 3)) return 0;
+  return mr::sh_shade_backward_ws(B, W, H);
+}
+
+int mr_sh_shade_backward(const float *drgba, const float *normals, const float *diffuse, int pixel_stride,
+                         const float *alphas, const float *sh, int B, int W, int H, int flip, float *dnormals,
+                         float *ddiffuse, float *dalphas, float *dsh, void *workspace, size_t workspace_bytes,
+                         void *stream) {
+  if (bad_sh_dims(B, W, H, pixel_stride)) return MR_EINVAL;
+  if (B == 0) return MR_OK;
+  if (!drgba || !normals || !diffuse || !sh || ((uintptr_t)drgba & 15u) != 0) return MR_EINVAL;
+  if (dalphas && !alphas) return MR_EINVAL;  // a derived alpha has no gradient
+  if (dsh) {
+    const int rc = check_ws(workspace, workspace_bytes, mr::sh_shade_backward_ws(B, W, H));
+    if (rc != MR_OK) return rc;
+  }
+  return mr::launch_sh_shade_backward(drgba, normals, diffuse, pixel_stride, alphas, sh, B, W, H, flip != 0,
+                                      dnormals, ddiffuse, dalphas, dsh, workspace, (hipStream_t)stream);
 }
 
 int mr_tone_map(const float *image, int B, size_t elements_per_image, float gamma, int32_t *max_scratch,

@@ -239,6 +239,13 @@ int launch_antialias_backward(const float *dout, const float *image, const int32
                               const float *z, const float *clip, const int32_t *tris, const int32_t *opp, int B,
                               int V, int T, int W, int H, int C, float *dimage, float *dclip, void *ws,
                               hipStream_t s);
+// spherical-harmonics shading (sh_shade.hip)
+size_t sh_shade_backward_ws(int B, int W, int H);
+int launch_sh_shade_forward(const float *normals, const float *diffuse, int stride, const float *alphas,
+                            const float *sh, int B, int W, int H, int flip, float *rgba, hipStream_t s);
+int launch_sh_shade_backward(const float *drgba, const float *normals, const float *diffuse, int stride,
+                             const float *alphas, const float *sh, int B, int W, int H, int flip, float *dnormals,
+                             float *ddiffuse, float *dalphas, float *dsh, void *ws, hipStream_t s);
 int soft_max_lights();
 int launch_debug_soft_nearest(const float *p, const float *a, const float *b, int n, float *out, hipStream_t s);
 size_t soft_ws(int B, int V, int T, int W, int H);
