@@ -557,6 +557,33 @@ int mr_sh_shade_backward(const float *drgba, const float *normals, const float *
                          float *ddiffuse, float *dalphas, float *dsh, void *workspace, size_t workspace_bytes,
                          void *stream);
 
+/* ---- bilinear texture mapping (no reference counterpart) ---------------------------------
+ * Samples a texture at a pixel buffer of UV coordinates ("Texture mapping"), with the
+ * conventions of grid_sample(align_corners=False): texel (i, j) covers u in [j/Wt, (j+1)/Wt) and v in
+ * [i/Ht, (i+1)/Ht), row 0 is v = 0.  x = fl(fl(u * Wt) - 0.5f), y likewise (binary32, un-fused), x0 = floor(x),
+ * fx = x - x0; the value is the bilinear blend of the taps (y0,x0) (y0,x0+1) (y0+1,x0) (y0+1,x0+1), their indices
+ * wrapped (MR_TEXTURE_WRAP) or clamped to the edge (MR_TEXTURE_CLAMP).  A pixel is 0 in every channel, and passes
+ * no gradient, where mask <= 0.5, where u or v is not finite, or where |x| or |y| >= 2^24.
+ *   tex         [Ht,Wt,C] (tex_batched 0: shared by every image) or [B,Ht,Wt,C] (tex_batched 1) f32, 1 <= C <= 4
+ *   uv          [B,H,W,2] f32;  mask [B,H,W] f32 or NULL
+ *   out         [B,H,W,C] f32
+ * tex, out, dout and dtex 16-byte aligned, uv and duv 8-byte aligned.  B <= 65535, W * H <= 2^30,
+ * ceil(W / 64) * ceil(H / 16) <= 2^22 (the backward's 64 x 16 pixel tiles: only very thin images are refused),
+ * Ht, Wt <= 65536, Ht * Wt <= 2^28.
+ * Backward: dout [B,H,W,C] -> dtex (tex's shape; a shared texture sums over the batch) and duv [B,H,W,2], each
+ * optional (NULL = not wanted).  duv is written per pixel (0 where skipped) and is reproducible in either mode.
+ * dtex is a scatter: float atomics, or 64-bit fixed point under mr_set_deterministic(1), which needs the
+ * workspace (mr_texture_backward_workspace_bytes reports the need of the calling thread's current mode: 0
+ * in float mode). */
+#define MR_TEXTURE_WRAP 0
+#define MR_TEXTURE_CLAMP 1
+int mr_texture_forward(const float *tex, const float *uv, const float *mask, int tex_batched, int Ht, int Wt, int C,
+                       int B, int W, int H, int boundary, float *out, void *stream);
+size_t mr_texture_backward_workspace_bytes(int tex_batched, int Ht, int Wt, int C, int B, int W, int H);
+int mr_texture_backward(const float *dout, const float *tex, const float *uv, const float *mask, int tex_batched,
+                        int Ht, int Wt, int C, int B, int W, int H, int boundary, float *dtex, float *duv,
+                        void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- clip-space transforms --------------------------------------------------------------
  * perspective(aspect, fov_y, near, far) . look_at(eye, center, up) per image, the product render() and
  * rasterize() apply to the vertices (src/common/camera_utils.py:45-139; src/mesh_renderer/render.py
@@ -603,7 +630,7 @@ int mr_tone_map(const float *image, int B, size_t elements_per_image, float gamm
  * number.  mr_soft_backward is covered as well (fixed-point integer atomics into 64-bit copies of its
  * four vertex outputs, scaled for the 1 / sigma and 1 / gamma its contributions carry; its light
  * gradients are fixed-order sums in either mode).  mr_antialias_backward is covered (fixed-point integer atomics for dclip, scaled from a first pass that finds
- * its largest per-vertex contribution).  mr_sh_shade_backward has no atomics and is bit-reproducible in either mode.  Not covered, float atomics remain: the composed
+ * its largest per-vertex contribution).  mr_sh_shade_backward has no atomics and is bit-reproducible in either mode.  mr_texture_backward is covered (fixed-point integer adds, in LDS and in the workspace, for dtex, scaled from a first pass that finds the largest upstream gradient and from the number of pixels that sample one texture; duv is per pixel in either mode).  Not covered, float atomics remain: the composed
  * interpolation backward (mr_interpolate_backward, the path for more than 16 attributes).  mr_l1_loss_forward is always deterministic.  Returns the previous setting. */
 int mr_set_deterministic(int on);
 

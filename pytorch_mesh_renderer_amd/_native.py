@@ -32,8 +32,8 @@ _deterministic = False
 
 
 def set_deterministic(on):
-    """Bit-reproducible gradients for the fused render / rasterize backward passes and the silhouette
-    antialiasing backward (mesh_renderer.antialias) (see
+    """Bit-reproducible gradients for the fused render / rasterize backward passes, the silhouette
+    antialiasing backward (mesh_renderer.antialias) and the texture gradient of mesh_renderer.texture (see
     mr_set_deterministic in include/mesh_raster.h): fixed-point integer accumulation instead of float
     atomics, ~10 % slower.  Process-wide on the Python side: the flag is handed to the library by
     whichever thread launches a backward kernel (autograd runs them on its own thread).  Returns the
@@ -265,6 +265,16 @@ def lib():
         L.mr_sh_shade_backward_workspace_bytes.restype = sz
         L.mr_sh_shade_backward.argtypes = [vp, vp, vp, ci, vp, vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, sz, vp]
         L.mr_sh_shade_backward.restype = ci
+        try:
+            L.mr_texture_forward.argtypes = [vp] * 3 + [ci] * 8 + [vp, vp]
+            L.mr_texture_forward.restype = ci
+            L.mr_texture_backward_workspace_bytes.argtypes = [ci] * 7
+            L.mr_texture_backward_workspace_bytes.restype = sz
+            L.mr_texture_backward.argtypes = [vp] * 4 + [ci] * 8 + [vp, vp, vp, sz, vp]
+            L.mr_texture_backward.restype = ci
+        except AttributeError as e:   # the texture entry points came without an ABI version bump
+            raise NativeLibraryError("%s lacks the texture entry points (%s): rebuild it (make -C "
+                                     "pytorch_mesh_renderer_amd/csrc)" % (LIB_PATH, e))
         _lib = L
     return _lib
 
@@ -907,6 +917,73 @@ def sh_shade_backward(drgba, normals, diffuse, alphas, sh, flip=True, want_norma
     if packed_grad and dpacked is not None:
         return dpacked, dalphas, dsh
     return dnormals, ddiffuse, dalphas, dsh
+
+
+TEXTURE_BOUNDARY = {"wrap": 0, "clamp": 1}   # mesh_raster.h, MR_TEXTURE_WRAP / MR_TEXTURE_CLAMP
+
+
+def _chk_texture(tex, uv, mask, boundary_mode):
+    """-> (B, H, W, Ht, Wt, C, tex_batched, boundary code)."""
+    _chk("uv", uv, _F32, None, None, None, 2)
+    B, H, W, _ = uv.shape
+    if torch.is_tensor(tex) and tex.dim() == 4:
+        _chk("texture", tex, _F32, B, None, None, None)
+    else:
+        _chk("texture", tex, _F32, None, None, None)
+    Ht, Wt, C = tex.shape[-3:]
+    if not 1 <= C <= 4 or Ht < 1 or Wt < 1:
+        raise ValueError("texture must have 1 to 4 channels and at least one texel, got shape %s" % list(tex.shape))
+    if mask is not None:
+        _chk("mask", mask, _F32, B, H, W)
+    if boundary_mode not in TEXTURE_BOUNDARY:
+        raise ValueError("boundary_mode must be 'wrap' or 'clamp', got %r" % (boundary_mode,))
+    tiles = ((W + 63) // 64) * ((H + 15) // 16)   # the backward's 64 x 16 pixel tiles
+    if B > 65535 or H * W > 1 << 30 or tiles > 1 << 22 or Ht > 65536 or Wt > 65536 or Ht * Wt > 1 << 28:
+        raise ValueError("texture sampling takes at most 65535 images of at most 2^30 pixels (and at most 2^22 tiles "
+                         "of 64 x 16 pixels) and textures of at most 65536 x 65536, 2^28 texels; got uv %s, texture %s"
+                         % (list(uv.shape), list(tex.shape)))
+    return B, H, W, Ht, Wt, C, int(tex.dim() == 4), TEXTURE_BOUNDARY[boundary_mode]
+
+
+def texture_forward(tex, uv, mask=None, boundary_mode="wrap"):
+    """tex [Ht,Wt,C] or [B,Ht,Wt,C] f32 (1 <= C <= 4), uv [B,H,W,2] f32, mask [B,H,W] f32 or None -> [B,H,W,C]
+    bilinear samples ("Texture mapping")."""
+    B, H, W, Ht, Wt, C, batched, boundary = _chk_texture(tex, uv, mask, boundary_mode)
+    dev = _require_device(*[t for t in (tex, uv, mask) if t is not None])
+    L = lib()
+    tex, uv = _aligned16(tex.contiguous()), _aligned16(uv.contiguous())
+    mask = mask.contiguous() if mask is not None else None
+    out = torch.empty(B, H, W, C, dtype=_F32, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.mr_texture_forward(_ptr(tex), _ptr(uv), _ptr(mask), batched, Ht, Wt, C, B, W, H, boundary, _ptr(out),
+                                  _stream(dev))
+    _check(rc, "mr_texture_forward")
+    return out
+
+
+def texture_backward(dout, tex, uv, mask=None, boundary_mode="wrap", want_tex=True, want_uv=True):
+    """-> (dtex with tex's shape, duv [B,H,W,2]); an unwanted gradient is None.  A shared texture's gradient is
+    summed over the batch."""
+    B, H, W, Ht, Wt, C, batched, boundary = _chk_texture(tex, uv, mask, boundary_mode)
+    _chk("upstream gradient", dout, _F32, B, H, W, C)
+    dev = _require_device(*[t for t in (dout, tex, uv, mask) if t is not None])
+    L = lib()
+    dout = _aligned16(dout.contiguous())
+    tex, uv = _aligned16(tex.contiguous()), _aligned16(uv.contiguous())
+    mask = mask.contiguous() if mask is not None else None
+    dtex = torch.empty(tex.shape, dtype=_F32, device=dev) if want_tex else None
+    duv = torch.empty(B, H, W, 2, dtype=_F32, device=dev) if want_uv else None
+    if B == 0 or not (want_tex or want_uv):
+        return (dtex.zero_() if dtex is not None else None), duv
+    with torch.cuda.device(dev):
+        _sync_deterministic()
+        ws, have = None, 0
+        if want_tex:
+            ws, have = _workspace(dev, L.mr_texture_backward_workspace_bytes(batched, Ht, Wt, C, B, W, H))
+        rc = L.mr_texture_backward(_ptr(dout), _ptr(tex), _ptr(uv), _ptr(mask), batched, Ht, Wt, C, B, W, H,
+                                   boundary, _ptr(dtex), _ptr(duv), _ptr(ws), have, _stream(dev))
+    _check(rc, "mr_texture_backward")
+    return dtex, duv
 
 
 def shade_backward(drgba, ids, bary, clip, normals, positions, diffuse, triangles, light_positions,

@@ -55,6 +55,34 @@ def sphere(radius, resolution=25):
     return vertices, torch.from_numpy(t), normals
 
 
+def sphere_uvs(resolution=25):
+    """Texture coordinates for sphere(radius, resolution): (uvs [3T,2] f32, uv_triangles [T,3] i32), one UV per
+    triangle corner, for render_textured(..., uv_triangles=uv_triangles).
+
+    Equirectangular: with d = p / |p| the corner's direction, v = 1 - acos(d_y) / pi (0 at the bottom pole) and
+    u = atan2(d_x, d_z) / (2 pi) taken into [0, 1).  Per corner rather than per vertex, so that the longitude
+    seam and the pole fans can be mapped without a jump: within a triangle whose corner u values span more than
+    0.5, 1 is added to the corners with u < 0.5 (sample with boundary_mode="wrap"), and a pole corner
+    (|d_y| = 1) takes the mean u of the triangle's corners that are not poles."""
+    v, t, _ = sphere_arrays(1.0, resolution)
+    p = v.astype(np.float64)[t]                                       # [T,3,3]
+    d = p / np.linalg.norm(p, axis=-1, keepdims=True)
+    vv = 1.0 - np.arccos(np.clip(d[..., 1], -1.0, 1.0)) / np.pi
+    u = np.mod(np.arctan2(d[..., 0], d[..., 2]) / (2.0 * np.pi), 1.0)
+    u = np.where(u >= 1.0, 0.0, u)
+    pole = np.abs(d[..., 1]) == 1.0
+    body = ~pole
+    hi = np.where(body, u, -np.inf).max(1)
+    lo = np.where(body, u, np.inf).min(1)
+    seam = (hi - lo > 0.5)[:, None] & body & (u < 0.5)
+    u = np.where(seam, u + 1.0, u)
+    mean = np.where(body, u, 0.0).sum(1) / np.maximum(body.sum(1), 1)
+    u = np.where(pole, mean[:, None], u)
+    uvs = np.stack([u, vv], -1).reshape(-1, 2).astype(np.float32)
+    uv_triangles = np.arange(3 * t.shape[0], dtype=np.int32).reshape(-1, 3)
+    return torch.from_numpy(uvs), torch.from_numpy(uv_triangles)
+
+
 _CUBE_CORNERS = [[-1, -1, 1], [-1, -1, -1], [-1, 1, -1], [-1, 1, 1],
                  [1, -1, 1], [1, -1, -1], [1, 1, -1], [1, 1, 1]]
 _CUBE_FACES_CCW = [[2, 1, 0], [0, 3, 2], [6, 2, 3], [3, 7, 6], [5, 6, 7], [7, 4, 5],

@@ -701,6 +701,46 @@ int mr_sh_shade_backward(const float *drgba, const float *normals, const float *
                                       dnormals, ddiffuse, dalphas, dsh, workspace, (hipStream_t)stream);
 }
 
+inline bool bad_texture_dims(int tex_batched, int Ht, int Wt, int C, int B, int W, int H) {
+  return (tex_batched != 0 && tex_batched != 1) || Ht < 1 || Wt < 1 || Ht > 65536 || Wt > 65536 ||
+         (size_t)Ht * Wt > ((size_t)1 << 28) || C < 1 || C > 4 || B < 0 || B > 65535 || W < 1 || H < 1 ||
+         (size_t)W * H > ((size_t)1 << 30) ||
+         (size_t)((W + 63) / 64) * (size_t)((H + 15) / 16) > ((size_t)1 << 22);  // the backward's 64 x 16 tiles
+}
+
+inline bool bad_boundary(int boundary) { return boundary != MR_TEXTURE_WRAP && boundary != MR_TEXTURE_CLAMP; }
+
+inline bool misaligned(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
+
+int mr_texture_forward(const float *tex, const float *uv, const float *mask, int tex_batched, int Ht, int Wt, int C,
+                       int B, int W, int H, int boundary, float *out, void *stream) {
+  if (bad_texture_dims(tex_batched, Ht, Wt, C, B, W, H) || bad_boundary(boundary)) return MR_EINVAL;
+  if (B == 0) return MR_OK;
+  if (!tex || !uv || !out || misaligned(tex, 16) || misaligned(out, 16) || misaligned(uv, 8)) return MR_EINVAL;
+  return mr::launch_texture_forward(tex, tex_batched, Ht, Wt, C, uv, mask, B, W, H, boundary, out,
+                                    (hipStream_t)stream);
+}
+
+size_t mr_texture_backward_workspace_bytes(int tex_batched, int Ht, int Wt, int C, int B, int W, int H) {
+  if (bad_texture_dims(tex_batched, Ht, Wt, C, B, W, H)) return 0;
+  return mr::texture_backward_ws(tex_batched, Ht, Wt, C, B);
+}
+
+int mr_texture_backward(const float *dout, const float *tex, const float *uv, const float *mask, int tex_batched,
+                        int Ht, int Wt, int C, int B, int W, int H, int boundary, float *dtex, float *duv,
+                        void *workspace, size_t workspace_bytes, void *stream) {
+  if (bad_texture_dims(tex_batched, Ht, Wt, C, B, W, H) || bad_boundary(boundary)) return MR_EINVAL;
+  if (B == 0) return MR_OK;
+  if (!dout || !tex || !uv || misaligned(dout, 16) || misaligned(tex, 16) || misaligned(uv, 8)) return MR_EINVAL;
+  if ((dtex && misaligned(dtex, 16)) || (duv && misaligned(duv, 8))) return MR_EINVAL;
+  if (dtex) {
+    const int rc = check_ws(workspace, workspace_bytes, mr::texture_backward_ws(tex_batched, Ht, Wt, C, B));
+    if (rc != MR_OK) return rc;
+  }
+  return mr::launch_texture_backward(dout, tex, tex_batched, Ht, Wt, C, uv, mask, B, W, H, boundary, dtex, duv,
+                                     workspace, (hipStream_t)stream);
+}
+
 int mr_tone_map(const float *image, int B, size_t elements_per_image, float gamma, int32_t *max_scratch,
                 float *out_f32, uint8_t *out_u8, void *stream) {
   if (B < 0) return MR_EINVAL;

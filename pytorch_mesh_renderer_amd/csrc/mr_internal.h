@@ -246,6 +246,13 @@ int launch_sh_shade_forward(const float *normals, const float *diffuse, int stri
 int launch_sh_shade_backward(const float *drgba, const float *normals, const float *diffuse, int stride,
                              const float *alphas, const float *sh, int B, int W, int H, int flip, float *dnormals,
                              float *ddiffuse, float *dalphas, float *dsh, void *ws, hipStream_t s);
+// bilinear texture sampling (texture.hip)
+size_t texture_backward_ws(int tex_batched, int Ht, int Wt, int C, int B);
+int launch_texture_forward(const float *tex, int tex_batched, int Ht, int Wt, int C, const float *uv,
+                           const float *mask, int B, int W, int H, int boundary, float *out, hipStream_t s);
+int launch_texture_backward(const float *dout, const float *tex, int tex_batched, int Ht, int Wt, int C,
+                            const float *uv, const float *mask, int B, int W, int H, int boundary, float *dtex,
+                            float *duv, void *ws, hipStream_t s);
 int soft_max_lights();
 int launch_debug_soft_nearest(const float *p, const float *a, const float *b, int n, float *out, hipStream_t s);
 size_t soft_ws(int B, int V, int T, int W, int H);

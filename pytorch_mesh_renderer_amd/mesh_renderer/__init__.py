@@ -3,6 +3,7 @@ from .render import render, tone_mapper, tone_mapper_uint8, to_uint8
 from .rasterize import rasterize
 from .antialiasing import antialias, antialias_topology
 from .sh_lighting import render_sh, sh_shader
+from .texturing import render_textured, texture
 from . import losses
 from .graphs import capture_step, CapturedStep
 
