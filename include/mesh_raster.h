@@ -584,6 +584,44 @@ int mr_texture_backward(const float *dout, const float *tex, const float *uv, co
                         int Ht, int Wt, int C, int B, int W, int H, int boundary, float *dtex, float *duv,
                         void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- mesh regularisers (no reference counterpart in the library; the reference's example7b.py has two) ----
+ * Uniform Laplacian, edge length and normal consistency of a batch of meshes that share one topology
+ * ("Mesh regularisers"), per image b:
+ *   lap  = 1/V sum_i |delta_i|,  delta_i = 1/deg_i sum_{j in N(i)} v_j - v_i   (0 for a vertex without neighbours)
+ *   edge = 1/E sum_e |v_lo - v_hi|   (use_target 0)   or   1/E sum_e (|v_lo - v_hi| - target_length)^2   (nonzero)
+ *   nc   = 1/F sum_flaps (1 - cos(n0, n1)),  n0 = (b-a) x (c-a),  n1 = (d-a) x (b-a);  a flap with |n0| <= 1e-8 or
+ *          |n1| <= 1e-8 has value 0 and gradient 0 and still counts in F
+ * A zero delta_i and a zero-length edge have gradient 0; E = 0 and F = 0 give 0.
+ *   vertices     [B,V,3] f32
+ *   nbr_offsets  [V+1] i32, nbr [2E] i32: CSR of every vertex's neighbours (each undirected edge appears at both
+ *                ends; an edge is counted at the end with the lower index)
+ *   flaps        [F,4] i32 (a, b, c, d): one row per edge (a, b) shared by exactly two triangles, c and d the
+ *                opposite corners
+ *   role_offsets [V+1] i32, roles [4F] i32: CSR of every vertex's (flap, role) pairs, entry = 4 * flap + role
+ *                (role 0..3 = a..d); the backward only
+ *   terms        bit mask of MR_MESH_*: a term that is not asked for is not computed and reads 0
+ *   unit_dirs    [B,V,3] f32: delta_i / |delta_i| (0 where delta_i = 0), written by the forward and read by the
+ *                backward; needed with MR_MESH_LAPLACIAN only
+ *   out_terms    [B,3] f32 out: (lap, edge, nc)
+ *   dterms       [B,3] f32 (device);  dvertices [B,V,3] f32 out, written completely
+ * 1 <= B <= 65535, 1 <= V <= 2^28, 0 <= E, F <= 2^28; sizes outside are MR_EINVAL (the workspace query returns
+ * 0).  An index outside [0, V) in nbr or flaps skips that neighbour or flap.  Gather form, eight lanes per vertex,
+ * no atomics and no zero-fills: each workgroup sums its part into one workspace row (forward only; needed unless
+ * terms is 0) and a second launch adds an image's rows in a fixed order, so the results are bit-reproducible in
+ * either deterministic mode and an image's terms do not depend on the rest of the batch. */
+#define MR_MESH_LAPLACIAN 1
+#define MR_MESH_EDGE 2
+#define MR_MESH_NORMAL 4
+size_t mr_mesh_regularizer_workspace_bytes(int B, int V, int F);
+int mr_mesh_regularizer_forward(const float *vertices, const int32_t *nbr_offsets, const int32_t *nbr,
+                                const int32_t *flaps, int B, int V, int E, int F, int terms, int use_target,
+                                float target_length, float *unit_dirs, float *out_terms, void *workspace,
+                                size_t workspace_bytes, void *stream);
+int mr_mesh_regularizer_backward(const float *dterms, const float *vertices, const float *unit_dirs,
+                                 const int32_t *nbr_offsets, const int32_t *nbr, const int32_t *flaps,
+                                 const int32_t *role_offsets, const int32_t *roles, int B, int V, int E, int F,
+                                 int terms, int use_target, float target_length, float *dvertices, void *stream);
+
 /* ---- clip-space transforms --------------------------------------------------------------
  * perspective(aspect, fov_y, near, far) . look_at(eye, center, up) per image, the product render() and
  * rasterize() apply to the vertices (src/common/camera_utils.py:45-139; src/mesh_renderer/render.py
@@ -630,7 +668,7 @@ int mr_tone_map(const float *image, int B, size_t elements_per_image, float gamm
  * number.  mr_soft_backward is covered as well (fixed-point integer atomics into 64-bit copies of its
  * four vertex outputs, scaled for the 1 / sigma and 1 / gamma its contributions carry; its light
  * gradients are fixed-order sums in either mode).  mr_antialias_backward is covered (fixed-point integer atomics for dclip, scaled from a first pass that finds
- * its largest per-vertex contribution).  mr_sh_shade_backward has no atomics and is bit-reproducible in either mode.  mr_texture_backward is covered (fixed-point integer adds, in LDS and in the workspace, for dtex, scaled from a first pass that finds the largest upstream gradient and from the number of pixels that sample one texture; duv is per pixel in either mode).  Not covered, float atomics remain: the composed
+ * its largest per-vertex contribution).  mr_sh_shade_backward has no atomics and is bit-reproducible in either mode, and so are mr_mesh_regularizer_forward / _backward.  mr_texture_backward is covered (fixed-point integer adds, in LDS and in the workspace, for dtex, scaled from a first pass that finds the largest upstream gradient and from the number of pixels that sample one texture; duv is per pixel in either mode).  Not covered, float atomics remain: the composed
  * interpolation backward (mr_interpolate_backward, the path for more than 16 attributes).  mr_l1_loss_forward is always deterministic.  Returns the previous setting. */
 int mr_set_deterministic(int on);
 

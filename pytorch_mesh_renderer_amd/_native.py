@@ -275,6 +275,16 @@ def lib():
         except AttributeError as e:   # the texture entry points came without an ABI version bump
             raise NativeLibraryError("%s lacks the texture entry points (%s): rebuild it (make -C "
                                      "pytorch_mesh_renderer_amd/csrc)" % (LIB_PATH, e))
+        try:
+            L.mr_mesh_regularizer_workspace_bytes.argtypes = [ci] * 3
+            L.mr_mesh_regularizer_workspace_bytes.restype = sz
+            L.mr_mesh_regularizer_forward.argtypes = [vp] * 4 + [ci] * 6 + [cf, vp, vp, vp, sz, vp]
+            L.mr_mesh_regularizer_forward.restype = ci
+            L.mr_mesh_regularizer_backward.argtypes = [vp] * 8 + [ci] * 6 + [cf, vp, vp]
+            L.mr_mesh_regularizer_backward.restype = ci
+        except AttributeError as e:   # the regulariser entry points came without an ABI version bump
+            raise NativeLibraryError("%s lacks the mesh regulariser entry points (%s): rebuild it (make -C "
+                                     "pytorch_mesh_renderer_amd/csrc)" % (LIB_PATH, e))
         _lib = L
     return _lib
 
@@ -760,6 +770,150 @@ def antialias_topology(triangles, vertex_count):
     except AttributeError:
         pass
     return opposite
+
+
+class MeshTopology:
+    """What the mesh regularisers need of a triangle array (mesh_topology()): int32 tensors on the triangles'
+    device and the three counts as Python ints.
+      edges [E,2]          unique undirected edges (lo, hi), lo < hi, ascending
+      nbr_offsets [V+1], nbr [2E]      CSR of every vertex's neighbours, ascending
+      flaps [F,4]          (a, b, c, d) per edge that exactly two (triangle, edge) rows share, in the edges' order
+      role_offsets [V+1], roles [4F]   CSR of every vertex's flap roles, entry = 4 * flap + role (0..3 = a..d)"""
+    __slots__ = ("vertex_count", "edge_count", "flap_count", "edges", "nbr_offsets", "nbr", "flaps", "role_offsets",
+                 "roles")
+
+    def __init__(self, vertex_count, edges, nbr_offsets, nbr, flaps, role_offsets, roles):
+        self.vertex_count, self.edge_count, self.flap_count = int(vertex_count), edges.shape[0], flaps.shape[0]
+        self.edges, self.nbr_offsets, self.nbr = edges, nbr_offsets, nbr
+        self.flaps, self.role_offsets, self.roles = flaps, role_offsets, roles
+
+    def tensors(self):
+        return (self.edges, self.nbr_offsets, self.nbr, self.flaps, self.role_offsets, self.roles)
+
+
+def _csr_by_vertex(owner, vertex_count):
+    """owner [n] i64 (a vertex per entry) -> (offsets [V+1] i32, order [n] i64): the entries grouped by vertex,
+    each group in the entries' own order."""
+    order = torch.argsort(owner, stable=True)
+    counts = torch.zeros(vertex_count, dtype=torch.int64, device=owner.device)
+    counts.scatter_add_(0, owner, torch.ones_like(owner))
+    offsets = torch.zeros(vertex_count + 1, dtype=torch.int64, device=owner.device)
+    offsets[1:] = torch.cumsum(counts, 0)
+    return offsets.to(torch.int32), order
+
+
+def mesh_topology(triangles, vertex_count):
+    """MeshTopology of a [T,3] triangle array of any integer dtype, on its device ("Mesh
+    regularisers").  A triangle with an index outside [0, V) is dropped whole, as k_vertex_normals drops it.
+    Edges are the unordered vertex pairs of the remaining triangles' sides (a side whose two indices are equal is
+    no edge); an edge that exactly two (triangle, side) rows share gives a flap (a, b, c, d) with c the opposite
+    corner of the earlier row, unless c or d is a or b (a triangle that repeats an index).  Boundary and
+    non-manifold edges give none.  Torch ops (sort + unique): no hot path, it runs on the CPU too, and it reads
+    the counts back to the host -- build it before a graph capture.  Cached on the tensor object like
+    vertex_adjacency."""
+    vertex_count = int(vertex_count)
+    key = (triangles._version, vertex_count, triangles.data_ptr())
+    cached = getattr(triangles, "_mr_mesh_topology", None)
+    if cached is not None and cached[0] == key:
+        return cached[1]
+    dev = triangles.device
+    V = vertex_count
+    tris = triangles.to(torch.int64).reshape(-1, 3)
+    tris = tris[((tris >= 0) & (tris < V)).all(dim=1)]
+    # side k of a triangle joins corners k+1 and k+2 and lies opposite corner k; one row per (triangle, side)
+    p = tris[:, [1, 2, 0]].reshape(-1)
+    q = tris[:, [2, 0, 1]].reshape(-1)
+    opp = tris.reshape(-1)
+    lo, hi = torch.minimum(p, q), torch.maximum(p, q)
+    keep = lo != hi
+    lo, hi, opp = lo[keep], hi[keep], opp[keep]
+    ekey = lo * max(V, 1) + hi
+    order = torch.argsort(ekey, stable=True)
+    sorted_key, sorted_opp = ekey[order], opp[order]
+    unique_key, counts = torch.unique_consecutive(sorted_key, return_counts=True)
+    edges = torch.stack([unique_key // max(V, 1), unique_key % max(V, 1)], dim=1)
+    first = torch.cumsum(counts, 0) - counts
+    pair = counts == 2
+    a, b = edges[pair, 0], edges[pair, 1]
+    c, d = sorted_opp[first[pair]], sorted_opp[(first[pair] + 1).clamp(max=max(sorted_opp.shape[0] - 1, 0))]
+    proper = (c != a) & (c != b) & (d != a) & (d != b)
+    flaps = torch.stack([a, b, c, d], dim=1)[proper]
+    src = torch.cat([edges[:, 0], edges[:, 1]])
+    dst = torch.cat([edges[:, 1], edges[:, 0]])
+    by_pair = torch.argsort(src * max(V, 1) + dst)
+    nbr_offsets, _ = _csr_by_vertex(src, V)
+    nbr = dst[by_pair]
+    role_offsets, roles = _csr_by_vertex(flaps.reshape(-1), V)
+    i32 = lambda t: t.to(torch.int32).contiguous()
+    topology = MeshTopology(V, i32(edges), nbr_offsets, i32(nbr), i32(flaps), role_offsets, i32(roles))
+    try:
+        triangles._mr_mesh_topology = (key, topology)
+    except AttributeError:
+        pass
+    return topology
+
+
+MESH_LAPLACIAN, MESH_EDGE, MESH_NORMAL = 1, 2, 4   # mesh_raster.h, MR_MESH_*
+
+
+def _chk_mesh_reg(vertices, topology, terms):
+    _chk("vertices", vertices, _F32, None, None, 3)
+    B, V, _ = vertices.shape
+    if not isinstance(topology, MeshTopology) or topology.vertex_count != V:
+        raise ValueError("topology must be the mesh_topology() of the triangles and of these %d vertices" % V)
+    if not 0 <= int(terms) <= 7:
+        raise ValueError("terms must be a mask of MESH_LAPLACIAN | MESH_EDGE | MESH_NORMAL, got %r" % (terms,))
+    if not 1 <= B <= 65535 or V < 1:
+        raise ValueError("the mesh regularisers take 1..65535 images of at least one vertex, got %s"
+                         % list(vertices.shape))
+    E, F = topology.edge_count, topology.flap_count
+    _chk("neighbour offsets", topology.nbr_offsets, _I32, V + 1)
+    _chk("neighbours", topology.nbr, _I32, 2 * E)
+    _chk("flaps", topology.flaps, _I32, F, 4)
+    _chk("flap role offsets", topology.role_offsets, _I32, V + 1)
+    _chk("flap roles", topology.roles, _I32, 4 * F)
+    return B, V, E, F
+
+
+def mesh_regularizer_forward(vertices, topology, terms, target_length=None):
+    """vertices [B,V,3] f32, topology: mesh_topology() -> (terms [B,3] = (lap, edge, nc), unit_dirs [B,V,3] or None
+    without MESH_LAPLACIAN).  A term outside the mask `terms` is not computed and reads 0."""
+    B, V, E, F = _chk_mesh_reg(vertices, topology, terms)
+    dev = _require_device(vertices, *topology.tensors())
+    L = lib()
+    vertices = vertices.contiguous()
+    out = torch.empty(B, 3, dtype=_F32, device=dev)
+    unit_dirs = torch.empty(B, V, 3, dtype=_F32, device=dev) if terms & MESH_LAPLACIAN else None
+    with torch.cuda.device(dev):
+        ws, have = _workspace(dev, L.mr_mesh_regularizer_workspace_bytes(B, V, F)) if terms else (None, 0)
+        rc = L.mr_mesh_regularizer_forward(
+            _ptr(vertices), _ptr(topology.nbr_offsets), _ptr(topology.nbr), _ptr(topology.flaps), B, V, E, F,
+            int(terms), 0 if target_length is None else 1, 0.0 if target_length is None else float(target_length),
+            _ptr(unit_dirs), _ptr(out), _ptr(ws), have, _stream(dev))
+    _check(rc, "mr_mesh_regularizer_forward")
+    return out, unit_dirs
+
+
+def mesh_regularizer_backward(dterms, vertices, unit_dirs, topology, terms, target_length=None):
+    """dterms [B,3] f32 (device) -> dvertices [B,V,3]; unit_dirs as the forward returned them."""
+    B, V, E, F = _chk_mesh_reg(vertices, topology, terms)
+    _chk("upstream gradient", dterms, _F32, B, 3)
+    if terms & MESH_LAPLACIAN:
+        _chk("unit directions", unit_dirs, _F32, B, V, 3)
+    tensors = [dterms, vertices] + ([unit_dirs] if terms & MESH_LAPLACIAN else []) + list(topology.tensors())
+    dev = _require_device(*tensors)
+    L = lib()
+    dterms, vertices = dterms.contiguous(), vertices.contiguous()
+    unit_dirs = unit_dirs.contiguous() if terms & MESH_LAPLACIAN else None
+    dvertices = torch.empty(B, V, 3, dtype=_F32, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.mr_mesh_regularizer_backward(
+            _ptr(dterms), _ptr(vertices), _ptr(unit_dirs), _ptr(topology.nbr_offsets), _ptr(topology.nbr),
+            _ptr(topology.flaps), _ptr(topology.role_offsets), _ptr(topology.roles), B, V, E, F, int(terms),
+            0 if target_length is None else 1, 0.0 if target_length is None else float(target_length),
+            _ptr(dvertices), _stream(dev))
+    _check(rc, "mr_mesh_regularizer_backward")
+    return dvertices
 
 
 def _aligned16(t):

@@ -701,6 +701,47 @@ int mr_sh_shade_backward(const float *drgba, const float *normals, const float *
                                       dnormals, ddiffuse, dalphas, dsh, workspace, (hipStream_t)stream);
 }
 
+inline bool bad_mesh_reg_dims(int B, int V, int E, int F, int terms) {
+  return B < 1 || B > 65535 || V < 1 || E < 0 || F < 0 || V > (1 << 28) || E > (1 << 28) || F > (1 << 28) ||
+         terms < 0 || terms > (MR_MESH_LAPLACIAN | MR_MESH_EDGE | MR_MESH_NORMAL);
+}
+
+size_t mr_mesh_regularizer_workspace_bytes(int B, int V, int F) {
+  if (bad_mesh_reg_dims(B, V, 0, F, 0)) return 0;
+  return mr::mesh_regularizer_ws(B, V, F);
+}
+
+int mr_mesh_regularizer_forward(const float *vertices, const int32_t *nbr_offsets, const int32_t *nbr,
+                                const int32_t *flaps, int B, int V, int E, int F, int terms, int use_target,
+                                float target_length, float *unit_dirs, float *out_terms, void *workspace,
+                                size_t workspace_bytes, void *stream) {
+  if (bad_mesh_reg_dims(B, V, E, F, terms)) return MR_EINVAL;
+  if (!vertices || !out_terms) return MR_EINVAL;
+  if ((terms & (MR_MESH_LAPLACIAN | MR_MESH_EDGE)) && (!nbr_offsets || (E > 0 && !nbr))) return MR_EINVAL;
+  if ((terms & MR_MESH_LAPLACIAN) && !unit_dirs) return MR_EINVAL;
+  if ((terms & MR_MESH_NORMAL) && F > 0 && !flaps) return MR_EINVAL;
+  if (terms != 0) {
+    const int rc = check_ws(workspace, workspace_bytes, mr::mesh_regularizer_ws(B, V, F));
+    if (rc != MR_OK) return rc;
+  }
+  return mr::launch_mesh_regularizer_forward(vertices, nbr_offsets, nbr, flaps, B, V, E, F, terms, use_target != 0,
+                                             target_length, unit_dirs, out_terms, workspace, (hipStream_t)stream);
+}
+
+int mr_mesh_regularizer_backward(const float *dterms, const float *vertices, const float *unit_dirs,
+                                 const int32_t *nbr_offsets, const int32_t *nbr, const int32_t *flaps,
+                                 const int32_t *role_offsets, const int32_t *roles, int B, int V, int E, int F,
+                                 int terms, int use_target, float target_length, float *dvertices, void *stream) {
+  if (bad_mesh_reg_dims(B, V, E, F, terms)) return MR_EINVAL;
+  if (!dterms || !vertices || !dvertices) return MR_EINVAL;
+  if ((terms & (MR_MESH_LAPLACIAN | MR_MESH_EDGE)) && (!nbr_offsets || (E > 0 && !nbr))) return MR_EINVAL;
+  if ((terms & MR_MESH_LAPLACIAN) && !unit_dirs) return MR_EINVAL;
+  if ((terms & MR_MESH_NORMAL) && F > 0 && (!flaps || !role_offsets || !roles)) return MR_EINVAL;
+  return mr::launch_mesh_regularizer_backward(dterms, vertices, unit_dirs, nbr_offsets, nbr, flaps, role_offsets,
+                                              roles, B, V, E, F, terms, use_target != 0, target_length, dvertices,
+                                              (hipStream_t)stream);
+}
+
 inline bool bad_texture_dims(int tex_batched, int Ht, int Wt, int C, int B, int W, int H) {
   return (tex_batched != 0 && tex_batched != 1) || Ht < 1 || Wt < 1 || Ht > 65536 || Wt > 65536 ||
          (size_t)Ht * Wt > ((size_t)1 << 28) || C < 1 || C > 4 || B < 0 || B > 65535 || W < 1 || H < 1 ||

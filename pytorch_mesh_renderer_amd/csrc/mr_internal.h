@@ -239,6 +239,16 @@ int launch_antialias_backward(const float *dout, const float *image, const int32
                               const float *z, const float *clip, const int32_t *tris, const int32_t *opp, int B,
                               int V, int T, int W, int H, int C, float *dimage, float *dclip, void *ws,
                               hipStream_t s);
+// mesh regularisers (mesh_reg.hip)
+size_t mesh_regularizer_ws(int B, int V, int F);
+int launch_mesh_regularizer_forward(const float *vertices, const int32_t *nbr_offsets, const int32_t *nbr,
+                                    const int32_t *flaps, int B, int V, int E, int F, int terms, int use_target,
+                                    float target, float *unit_dirs, float *out_terms, void *ws, hipStream_t s);
+int launch_mesh_regularizer_backward(const float *dterms, const float *vertices, const float *unit_dirs,
+                                     const int32_t *nbr_offsets, const int32_t *nbr, const int32_t *flaps,
+                                     const int32_t *role_offsets, const int32_t *roles, int B, int V, int E, int F,
+                                     int terms, int use_target, float target, float *dvertices, hipStream_t s);
+
 // spherical-harmonics shading (sh_shade.hip)
 size_t sh_shade_backward_ws(int B, int W, int H);
 int launch_sh_shade_forward(const float *normals, const float *diffuse, int stride, const float *alphas,

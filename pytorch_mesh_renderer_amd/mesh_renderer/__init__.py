@@ -5,6 +5,7 @@ from .antialiasing import antialias, antialias_topology
 from .sh_lighting import render_sh, sh_shader
 from .texturing import render_textured, texture
 from . import losses
+from . import regularizers
 from .graphs import capture_step, CapturedStep
 
 __version__ = '0.0.1'
