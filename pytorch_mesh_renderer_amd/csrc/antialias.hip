@@ -19,7 +19,7 @@
 // restatement reproduces the set of blended pairs exactly.  The edge functions are those of the rasterizer
 // (raster_forward.hip): the sign-normalised adjugate rows of [[x],[y],[w]].
 #include "mr_internal.h"
-#include "run_accum.h"
+#include "det_fixed.h"
 
 namespace mr {
 
@@ -271,7 +271,7 @@ template <int C, int MODE>
 __global__ __launch_bounds__(kAaThreads) void k_aa_backward(AaArgs a, const float *__restrict__ dout,
                                                             float *__restrict__ dimage, float *__restrict__ dclip,
                                                             long long *__restrict__ dclip_fixed,
-                                                            float *__restrict__ det_block) {
+                                                            DetBlock *__restrict__ det_block) {
   Hood h = load_hood(a, (int)blockIdx.x);
   const int nc = channels<C>(a);
   // up to four pairs where this lane's pixel is the modified one, two vertices each: (vertex, dL/d(x, y, w))
@@ -371,11 +371,11 @@ __global__ __launch_bounds__(kAaThreads) void k_aa_backward(AaArgs a, const floa
         atomicAdd(dst + 3, sw);  // the z column never receives gradient
       } else if (MODE == kModeMax) {
         const float big = fmaxf(fmaxf(fabsf(sx), fabsf(sy)), fabsf(sw));
-        atomicMax((int *)det_block + 4, __float_as_int(big != big ? INFINITY : big));
+        atomicMax(&det_block->max_bits, __float_as_int(big != big ? INFINITY : big));
       } else {
         long long *dst = dclip_fixed + (size_t)K * 4;
-        const float to_fixed = det_block[0];
-        int *overflow = det_overflow_flag(det_block);
+        const float to_fixed = det_block->to_fixed;
+        int *overflow = &det_block->overflow;
         atomic_add_fixed(dst + 0, sx, to_fixed, overflow);
         atomic_add_fixed(dst + 1, sy, to_fixed, overflow);
         atomic_add_fixed(dst + 3, sw, to_fixed, overflow);
@@ -386,13 +386,6 @@ __global__ __launch_bounds__(kAaThreads) void k_aa_backward(AaArgs a, const floa
     for (int s = 0; s < 8; ++s) mine |= key[s] >= 0;
     pending = __ballot(mine);
   }
-}
-
-__global__ __launch_bounds__(256) void k_aa_from_fixed(const long long *__restrict__ fixed, const float *__restrict__ det_block,
-                                                       size_t n, float *__restrict__ out) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  // a contribution did not fit the fixed-point range (run_accum.h, atomic_add_fixed): NaN, not garbage
-  if (i < n) out[i] = *det_overflow_flag(det_block) ? __int_as_float(0x7fc00000) : (float)fixed[i] * det_block[1];
 }
 
 AaArgs make_args(const float *image, const int32_t *ids, const float *bary, const float *z, const float *clip,
@@ -409,7 +402,7 @@ inline size_t fixed_bytes(int B, int V) { return align_up((size_t)B * V * 4 * si
 
 template <int MODE>
 int launch_backward_mode(const AaArgs &a, const float *dout, float *dimage, float *dclip, long long *fixed,
-                         float *det_block, hipStream_t s) {
+                         DetBlock *det_block, hipStream_t s) {
   const dim3 grid(aa_blocks(a.B, a.W, a.H)), block(kAaThreads);
   switch (a.C) {
     case 1: hipLaunchKernelGGL((k_aa_backward<1, MODE>), grid, block, 0, s, a, dout, dimage, dclip, fixed, det_block); break;
@@ -448,18 +441,13 @@ int launch_antialias_backward(const float *dout, const float *image, const int32
   const AaArgs a = make_args(image, ids, bary, z, clip, tris, opp, B, V, T, W, H, C);
   if (g_deterministic == 0) return launch_backward_mode<kModeFloat>(a, dout, dimage, dclip, nullptr, nullptr, s);
   long long *fixed = (long long *)ws;
-  float *det_block = (float *)((char *)ws + fixed_bytes(B, V));
+  DetBlock *det_block = (DetBlock *)((char *)ws + fixed_bytes(B, V));
   if (zero_async(ws, fixed_bytes(B, V) + kDetBlockBytes, s) != hipSuccess) return check_launch();
   int rc = launch_backward_mode<kModeMax>(a, dout, dimage, dclip, fixed, det_block, s);
   if (rc != MR_OK) return rc;
-  hipLaunchKernelGGL(k_det_scale_from_bits, dim3(1), dim3(1), 0, s, (const int *)det_block + 4, 1.0f, det_block);
-  if ((rc = check_launch()) != MR_OK) return rc;
+  if ((rc = launch_det_scale_of_max(det_block, 1.0f, s)) != MR_OK) return rc;
   if ((rc = launch_backward_mode<kModeFixed>(a, dout, dimage, dclip, fixed, det_block, s)) != MR_OK) return rc;
-  const size_t n = (size_t)B * V * 4;
-  if (n == 0) return MR_OK;
-  hipLaunchKernelGGL(k_aa_from_fixed, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const long long *)fixed,
-                     (const float *)det_block, n, dclip);
-  return check_launch();
+  return launch_det_to_float(fixed, det_block, dclip, (size_t)B * V * 4, s);
 }
 
 }  // namespace mr

@@ -379,10 +379,10 @@ struct AttrFoldLaneFn {
 
 // One thread per (image, vertex): sums the rows of the triangles incident to its vertex (CSR
 // adjacency: entry = 3 * triangle + corner).  Every output is written exactly once, no atomics.
-// DET (mr_set_deterministic): the rows hold 64-bit fixed-point sums (run_accum.h), converted here.
+// DET (mr_set_deterministic): the rows hold 64-bit fixed-point sums (det_fixed.h), converted here.
 template <int AP, bool DET>
 __global__ __launch_bounds__(kThreads) void k_attr_gather(
-    const float *__restrict__ acc, const float *__restrict__ det_scale, const int32_t *__restrict__ offsets,
+    const float *__restrict__ acc, const DetBlock *__restrict__ det, const int32_t *__restrict__ offsets,
     const int32_t *__restrict__ entries, int B, int V, int T, int A, float *__restrict__ dattrs,
     float *__restrict__ dclip) {
   constexpr int STRIDE = AttrRowsFn<AP>::kStride;
@@ -400,14 +400,14 @@ __global__ __launch_bounds__(kThreads) void k_attr_gather(
     const float *row = acc + ((size_t)b * T + t) * STRIDE;
     const long long *row_x = (const long long *)acc + ((size_t)b * T + t) * STRIDE;
 #pragma unroll
-    for (int j = 0; j < AP; ++j) a[j] += DET ? (float)row_x[k * AP + j] * det_scale[1] : row[k * AP + j];
+    for (int j = 0; j < AP; ++j) a[j] += DET ? det_to_float(row_x[k * AP + j], det) : row[k * AP + j];
 #pragma unroll
-    for (int j = 0; j < 3; ++j) c[j] += DET ? (float)row_x[3 * AP + k * 3 + j] * det_scale[1] : row[3 * AP + k * 3 + j];
+    for (int j = 0; j < 3; ++j) c[j] += DET ? det_to_float(row_x[3 * AP + k * 3 + j], det) : row[3 * AP + k * 3 + j];
   }
-  if (DET && *det_overflow_flag(det_scale)) {  // a contribution outside the fixed-point range: NaN, not garbage
+  if (DET && det->overflow) {  // also a vertex that no fixed-point sum feeds (det_fixed.h)
 #pragma unroll
-    for (int j = 0; j < AP; ++j) a[j] = __int_as_float(0x7fc00000);
-    c[0] = c[1] = c[2] = __int_as_float(0x7fc00000);
+    for (int j = 0; j < AP; ++j) a[j] = det_to_float(0, det);
+    c[0] = c[1] = c[2] = det_to_float(0, det);
   }
   float *dst = dattrs + (size_t)gid * A;
 #pragma unroll
@@ -456,7 +456,7 @@ int run(const float *dout, const int32_t *ids, const float *bary, const float *c
   p += align_up((size_t)B * T * sizeof(BwdRec), 256);
   float *corners = (float *)p;
   p += corner_bytes(B, T, AP);
-  float *det_block = (float *)p;
+  DetBlock *det_block = (DetBlock *)p;
   p += kDetBlockBytes;
   float *fold_recs = (float *)p;
   const bool det = g_deterministic != 0;

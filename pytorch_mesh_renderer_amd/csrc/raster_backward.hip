@@ -181,17 +181,21 @@ struct RasterLanesFn : RasterGradFn {
   }
 };
 
+// VAL = float: per-triangle sums -> float atomics into dclip; VAL = long long (deterministic mode): fixed-point
+// sums -> the fixed-point copy of dclip (integer atomics: order-free)
+template <class VAL>
 __global__ __launch_bounds__(kThreads) void k_bwd_scatter(
-    const float *__restrict__ acc, const int32_t *__restrict__ tris, int B, int V, int T,
-    float *__restrict__ dclip) {
+    const VAL *__restrict__ acc, const int32_t *__restrict__ tris, int B, int V, int T,
+    VAL *__restrict__ dclip) {
+  using ATOM = typename std::conditional<sizeof(VAL) == 8, unsigned long long, float>::type;
   const long gid = (long)blockIdx.x * kThreads + threadIdx.x;
   if (gid >= (long)B * T) return;
-  float a[9];
+  VAL a[9];
   bool any = false;
 #pragma unroll
   for (int k = 0; k < 9; ++k) {
     a[k] = acc[gid * kStride + k];
-    any |= (a[k] != 0.0f);  // NaN counts as touched
+    any |= (a[k] != (VAL)0);  // NaN counts as touched
   }
   if (!any) return;
   const int b = (int)(gid / T);
@@ -200,10 +204,10 @@ __global__ __launch_bounds__(kThreads) void k_bwd_scatter(
   for (int j = 0; j < 3; ++j) {
     const int vi = tris[3 * t + j];
     if ((unsigned)vi >= (unsigned)V) continue;
-    float *dst = dclip + ((long)b * V + vi) * 4;
-    atomicAdd(&dst[0], a[j * 3 + 0]);  // x
-    atomicAdd(&dst[1], a[j * 3 + 1]);  // y
-    atomicAdd(&dst[3], a[j * 3 + 2]);  // w; the z column never receives gradient
+    ATOM *dst = (ATOM *)dclip + ((long)b * V + vi) * 4;
+    atomicAdd(&dst[0], (ATOM)a[j * 3 + 0]);  // x
+    atomicAdd(&dst[1], (ATOM)a[j * 3 + 1]);  // y
+    atomicAdd(&dst[3], (ATOM)a[j * 3 + 2]);  // w; the z column never receives gradient
   }
 }
 
@@ -211,74 +215,13 @@ __global__ __launch_bounds__(kThreads) void k_bwd_scatter(
 inline size_t acc_bytes(int B, int T) { return align_up((size_t)B * T * kStride * sizeof(long long), 256); }
 inline size_t dclip_fixed_bytes(int B, int V) { return align_up((size_t)B * V * 4 * sizeof(long long), 256); }
 
-// ---- deterministic mode (mr_set_deterministic): fixed point end to end -----------------------
-__global__ __launch_bounds__(kThreads) void k_abs_max_f(const float *__restrict__ x, size_t n, int *__restrict__ max_bits) {
-  int best = 0;
-  for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (size_t)gridDim.x * kThreads)
-    best = max(best, __float_as_int(fabsf(x[i])));
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) best = max(best, __shfl_down(best, off));
-  // one atomic per WORKGROUP (thousands of wavefronts on one address queue up behind each other)
-  __shared__ int s_best[kThreads / kWave];
-  if ((threadIdx.x & (kWave - 1)) == 0) s_best[threadIdx.x >> 6] = best;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < kThreads / kWave; ++w) best = max(best, s_best[w]);
-    if (best != 0) atomicMax(max_bits, best);
-  }
-}
-
-__global__ void k_det_scale_from_max(const int *__restrict__ max_bits, float *__restrict__ det_scale) {
-  const float g = __int_as_float(max_bits[0]);
-  int e = 0;
-  if (g > 0.0f && g < INFINITY) (void)frexpf(g, &e);
-  const int k = min(max(41 - e, -100), 100);
-  det_scale[0] = ldexpf(1.0f, k);
-  det_scale[1] = ldexpf(1.0f, -k);
-}
-
-// per-triangle fixed-point sums -> per-vertex fixed-point sums (integer atomics: order-free)
-__global__ __launch_bounds__(kThreads) void k_bwd_scatter_fixed(
-    const long long *__restrict__ acc, const int32_t *__restrict__ tris, int B, int V, int T,
-    long long *__restrict__ dclip_fixed) {
-  const long gid = (long)blockIdx.x * kThreads + threadIdx.x;
-  if (gid >= (long)B * T) return;
-  long long a[9];
-  bool any = false;
-#pragma unroll
-  for (int k = 0; k < 9; ++k) {
-    a[k] = acc[gid * kStride + k];
-    any |= (a[k] != 0);
-  }
-  if (!any) return;
-  const int b = (int)(gid / T);
-  const int t = (int)(gid - (long)b * T);
-#pragma unroll
-  for (int j = 0; j < 3; ++j) {
-    const int vi = tris[3 * t + j];
-    if ((unsigned)vi >= (unsigned)V) continue;
-    unsigned long long *dst = (unsigned long long *)dclip_fixed + ((long)b * V + vi) * 4;
-    atomicAdd(&dst[0], (unsigned long long)a[j * 3 + 0]);
-    atomicAdd(&dst[1], (unsigned long long)a[j * 3 + 1]);
-    atomicAdd(&dst[3], (unsigned long long)a[j * 3 + 2]);
-  }
-}
-
-__global__ __launch_bounds__(kThreads) void k_from_fixed(const long long *__restrict__ fixed,
-                                                         const float *__restrict__ det_scale, long n,
-                                                         float *__restrict__ out) {
-  const long i = (long)blockIdx.x * kThreads + threadIdx.x;
-  // a contribution did not fit the fixed-point range (run_accum.h, atomic_add_fixed): NaN, not garbage
-  if (i < n) out[i] = *det_overflow_flag(det_scale) ? __int_as_float(0x7fc00000) : (float)fixed[i] * det_scale[1];
-}
-
 }  // namespace
 
 extern thread_local int g_deterministic;
 
 size_t raster_backward_ws(int B, int V, int T, int W, int H) {
   (void)W; (void)H;
-  return acc_bytes(B, T) + align_up((size_t)B * T * sizeof(BwdRec), 256) + dclip_fixed_bytes(B, V) + 256;
+  return acc_bytes(B, T) + align_up((size_t)B * T * sizeof(BwdRec), 256) + dclip_fixed_bytes(B, V) + kDetBlockBytes;
 }
 
 int launch_raster_backward(const float *dbary, const float *clip, const int32_t *tris,
@@ -297,27 +240,19 @@ int launch_raster_backward(const float *dbary, const float *clip, const int32_t 
   RasterGradFn fn{(const F3 *)dbary, ids, (const F3 *)bary, recs, T};
   if (det) {
     long long *dclip_fixed = (long long *)((char *)recs + align_up((size_t)B * T * sizeof(BwdRec), 256));
-    float *det_scale = (float *)((char *)dclip_fixed + dclip_fixed_bytes(B, V));
-    int *max_bits = (int *)(det_scale + 4);
-    if (zero_async(dclip_fixed, dclip_fixed_bytes(B, V) + 256, s) != hipSuccess) return check_launch();
-    const size_t n = (size_t)B * H * W * 3;
-    const size_t want = (n + kThreads - 1) / kThreads;
-    hipLaunchKernelGGL(k_abs_max_f, dim3((unsigned)(want < 2048 ? want : 2048)), dim3(kThreads), 0, s, dbary, n, max_bits);
-    if ((rc = check_launch()) != MR_OK) return rc;
-    hipLaunchKernelGGL(k_det_scale_from_max, dim3(1), dim3(1), 0, s, max_bits, det_scale);
-    if ((rc = check_launch()) != MR_OK) return rc;
+    DetBlock *det_block = (DetBlock *)((char *)dclip_fixed + dclip_fixed_bytes(B, V));
+    if (zero_async(dclip_fixed, dclip_fixed_bytes(B, V), s) != hipSuccess) return check_launch();
+    if ((rc = launch_det_scale(dbary, (size_t)B * H * W * 3, 1.0f, det_block, s)) != MR_OK) return rc;
     {
       KernelTimer timer(MR_TIMER_RASTER_BACKWARD, s);
-      rc = launch_accumulate_runs_fixed(fn, B, T, W, H, acc, det_scale, s);
+      rc = launch_accumulate_runs_fixed(fn, B, T, W, H, acc, det_block, s);
     }
     if (rc != MR_OK) return rc;
-    const long nbt = (long)B * T, nv4 = (long)B * V * 4;
-    hipLaunchKernelGGL(k_bwd_scatter_fixed, dim3((unsigned)((nbt + kThreads - 1) / kThreads)), dim3(kThreads), 0, s,
+    const long nbt = (long)B * T;
+    hipLaunchKernelGGL(k_bwd_scatter<long long>, dim3((unsigned)((nbt + kThreads - 1) / kThreads)), dim3(kThreads), 0, s,
                        (const long long *)acc, tris, B, V, T, dclip_fixed);
     if ((rc = check_launch()) != MR_OK) return rc;
-    hipLaunchKernelGGL(k_from_fixed, dim3((unsigned)((nv4 + kThreads - 1) / kThreads)), dim3(kThreads), 0, s,
-                       dclip_fixed, det_scale, nv4, dclip);
-    return check_launch();
+    return launch_det_to_float(dclip_fixed, det_block, dclip, (size_t)B * V * 4, s);
   }
   {
     KernelTimer timer(MR_TIMER_RASTER_BACKWARD, s);
@@ -326,8 +261,8 @@ int launch_raster_backward(const float *dbary, const float *clip, const int32_t 
   }
   if (rc != MR_OK) return rc;
   const long nbt = (long)B * T;
-  hipLaunchKernelGGL(k_bwd_scatter, dim3((unsigned)((nbt + kThreads - 1) / kThreads)), dim3(kThreads),
-                     0, s, acc, tris, B, V, T, dclip);
+  hipLaunchKernelGGL(k_bwd_scatter<float>, dim3((unsigned)((nbt + kThreads - 1) / kThreads)), dim3(kThreads),
+                     0, s, (const float *)acc, tris, B, V, T, dclip);
   return check_launch();
 }
 

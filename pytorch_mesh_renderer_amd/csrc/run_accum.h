@@ -37,6 +37,7 @@
 
 #include <type_traits>
 
+#include "det_fixed.h"
 #include "mr_internal.h"
 
 namespace mr {
@@ -48,70 +49,6 @@ constexpr int kRunThreads = 256;
 constexpr int kRunRowsPerWave = MR_RUN_ROWS_PER_WAVE;                 // pixels each lane walks (k_accumulate_runs)
 constexpr int kRunRegionH = kRunRowsPerWave * (kRunThreads / kWave);  // 128 rows / workgroup
 constexpr int kRunMaxProbe = 16;
-
-// Deterministic mode (mr_set_deterministic): sums are accumulated in 64-bit FIXED POINT with
-// integer atomics.  Integer addition is associative (also through two's-complement wrap-around),
-// so the result no longer depends on the order in which lanes and wavefronts commit: bit-identical
-// from run to run, where float atomics differ in the last bits.  det_scale[0] = 2^k converts to
-// fixed point (a power of two: exact), det_scale[1] = 2^-k back; k is derived on the device from the
-// largest upstream gradient g so that g maps to about 2^41: values down to g * 2^-42 are resolved and
-// a triangle's total may reach g * 2^21 before the 64-bit range ends.
-// A contribution that does not fit -- NaN, infinite, or beyond +-2^63 after scaling (1 / det of a
-// sliver triangle times a large upstream gradient) -- is not converted (the conversion of an
-// out-of-range float is garbage of arbitrary sign): it raises the launch's overflow flag instead,
-// det_overflow_flag(det_scale), and the pass that converts the sums back to float writes NaN
-// everywhere when the flag is set -- the float path's answer to such inputs, spread over the whole
-// output, instead of a finite wrong number.  (Sums of many in-range contributions still wrap
-// silently beyond 2^63: the scale leaves 2^21 of headroom over the largest upstream gradient.)
-__device__ __forceinline__ int *det_overflow_flag(const float *det_scale) { return (int *)det_scale + 8; }
-__device__ __forceinline__ void atomic_add_fixed(long long *p, float v, float to_fixed, int *overflow) {
-  const float x = v * to_fixed;
-  if (!(fabsf(x) < 9.0e18f)) {
-    atomicOr(overflow, 1);
-    return;
-  }
-  atomicAdd((unsigned long long *)p, (unsigned long long)__float2ll_rn(x));
-}
-
-// The deterministic mode's 512-byte side block (zeroed per launch): float [0] = 2^k, [1] = 2^-k,
-// int [4] = bits of the largest |upstream gradient|, int [8] = overflow flag (above).
-constexpr size_t kDetBlockBytes = 512;
-static __global__ __launch_bounds__(256) void k_det_abs_max(const float *__restrict__ x, size_t n, int *__restrict__ max_bits) {
-  int best = 0;  // non-negative floats order like integers; a NaN sorts on top
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256)
-    best = max(best, __float_as_int(fabsf(x[i])));
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) best = max(best, __shfl_down(best, off));
-  __shared__ int s_best[4];  // one atomic per WORKGROUP (thousands on one address queue up)
-  if ((threadIdx.x & 63) == 0) s_best[threadIdx.x >> 6] = best;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < 4; ++w) best = max(best, s_best[w]);
-    if (best != 0) atomicMax(max_bits, best);
-  }
-}
-// (2^k, 2^-k) with k such that `gain` times the largest upstream gradient maps to about 2^41
-static __global__ void k_det_scale_from_bits(const int *__restrict__ max_bits, float gain, float *__restrict__ det_scale) {
-  const float g = __int_as_float(max_bits[0]) * gain;
-  int e = 0;
-  if (g > 0.0f && g < INFINITY) (void)frexpf(g, &e);  // g = m * 2^e, m in [0.5, 1)
-  const int k = min(max(41 - e, -100), 100);
-  det_scale[0] = ldexpf(1.0f, k);
-  det_scale[1] = ldexpf(1.0f, -k);
-}
-// Zeroes the block and fills its scale pair from the n floats at x (the upstream gradient image).
-// gain: the largest factor a contribution may carry over the upstream gradient beyond the 2^21 of
-// headroom the scale leaves (1 for the rasterizer / shading passes; 1 / min(sigma, gamma) for SoftRas).
-inline int launch_det_scale(const float *x, size_t n, float gain, float *det_block, hipStream_t s) {
-  if (zero_async(det_block, kDetBlockBytes, s) != hipSuccess) return check_launch();
-  const size_t want = (n + 255) / 256;
-  hipLaunchKernelGGL(k_det_abs_max, dim3((unsigned)(want < 2048 ? (want ? want : 1) : 2048)), dim3(256), 0, s, x, n,
-                     (int *)det_block + 4);
-  int rc = check_launch();
-  if (rc != MR_OK) return rc;
-  hipLaunchKernelGGL(k_det_scale_from_bits, dim3(1), dim3(1), 0, s, (const int *)det_block + 4, gain, det_block);
-  return check_launch();
-}
 
 template <int SLOTS>
 __device__ __forceinline__ int run_find_slot(int *keys, int tri) {
@@ -144,14 +81,14 @@ __device__ __forceinline__ void run_flush(int *keys, VAL *vals, VAL *acc_img, in
 template <class Fn, bool DET>
 __global__ __launch_bounds__(kRunThreads, DET ? 1 : Fn::kMinWavesPerSimd) void k_accumulate_runs(
     Fn fn, int T, int W, int H, int regions_x, int regions_per_image, int n_regions,
-    int regions_per_xcd, float *__restrict__ acc, const float *__restrict__ det_scale) {
+    int regions_per_xcd, float *__restrict__ acc, const DetBlock *__restrict__ det) {
   constexpr int N = Fn::kN, STRIDE = Fn::kStride, SLOTS = Fn::kSlots;
   static_assert(N <= STRIDE, "accumulator row too small");
   using VAL = typename std::conditional<DET, long long, float>::type;
   __shared__ int s_keys[SLOTS];
   __shared__ VAL s_vals[SLOTS * N];
-  const float scale = DET ? det_scale[0] : 0.0f;
-  int *overflow = DET ? det_overflow_flag(det_scale) : nullptr;
+  const float scale = DET ? det->to_fixed : 0.0f;
+  int *overflow = DET ? det_overflow_flag(det) : nullptr;
 
   const int region = xcd_contiguous_block((int)blockIdx.x, n_regions, regions_per_xcd);
   if (region < 0) return;
@@ -284,7 +221,7 @@ constexpr int kRowsThreads = MR_ROWS_THREADS;
 template <class Fn, bool DET>
 __global__ __launch_bounds__(kRowsThreads, Fn::kMinWavesPerSimd) void k_accumulate_rows(
     Fn fn, int T, int W, int H, int regions_x, int regions_per_image, int n_regions,
-    int regions_per_xcd, float *__restrict__ acc, const float *__restrict__ det_scale) {
+    int regions_per_xcd, float *__restrict__ acc, const DetBlock *__restrict__ det) {
   constexpr int N = Fn::kN, STRIDE = Fn::kStride, F = Fn::kFactorStride;
   static_assert(F % 4 == 0 && Fn::kFactors <= F && N <= kWave && N <= STRIDE, "row layout");
   // Parked factors, FACTOR-major: row f holds factor f of the wavefront's 64 pixels, so that a
@@ -326,7 +263,7 @@ __global__ __launch_bounds__(kRowsThreads, Fn::kMinWavesPerSimd) void k_accumula
   const int y_end = min(y_begin + kRowsPerWave, H);
   float *acc_img = acc + (size_t)img * T * STRIDE;
   long long *acc_fixed = (long long *)acc + (size_t)img * T * STRIDE;  // DET: 8-byte elements
-  const float to_fixed = DET ? det_scale[0] : 0.0f;
+  const float to_fixed = DET ? det->to_fixed : 0.0f;
   float *stage = s_stage[wave];
   int ia, ib;  // the two factors whose product this lane sums (lanes >= N idle along)
   Fn::factor_pair(min(lane, N - 1), ia, ib);
@@ -338,7 +275,7 @@ __global__ __launch_bounds__(kRowsThreads, Fn::kMinWavesPerSimd) void k_accumula
   int merge_count = 0;   // slots in use, wave-uniform
   auto commit = [&](const int t, const float v) {  // one contiguous N-lane atomic into the triangle's row
     if (lane < N) {
-      if (DET) atomic_add_fixed(&acc_fixed[(size_t)t * STRIDE + lane], v, to_fixed, det_overflow_flag(det_scale));
+      if (DET) atomic_add_fixed(&acc_fixed[(size_t)t * STRIDE + lane], v, to_fixed, det_overflow_flag(det));
       else atomicAdd(&acc_img[(size_t)t * STRIDE + lane], v);
     }
   };
@@ -506,7 +443,7 @@ struct LanesSkipStrips<Fn, decltype((void)Fn::kSkipsStrips)> { static constexpr 
 template <class Fn, bool DET>
 __global__ __launch_bounds__(kWave, Fn::kMinWavesPerSimd) void k_accumulate_lanes(
     Fn fn, int T, int W, int H, int regions_x, int regions_per_image, int n_regions,
-    int regions_per_xcd, int rows_per_wave, float *__restrict__ acc, const float *__restrict__ det_scale) {
+    int regions_per_xcd, int rows_per_wave, float *__restrict__ acc, const DetBlock *__restrict__ det) {
   constexpr int N = Fn::kN, STRIDE = Fn::kStride, P = lanes_park_stride(N);
   static_assert(N <= kWave && N <= STRIDE, "one reduction lane per sum");
   __shared__ __attribute__((aligned(16))) float s_park[kWave * P];
@@ -535,7 +472,7 @@ __global__ __launch_bounds__(kWave, Fn::kMinWavesPerSimd) void k_accumulate_lane
   }
   float *acc_img = acc + (size_t)img * T * STRIDE;
   long long *acc_fixed = (long long *)acc + (size_t)img * T * STRIDE;  // DET: 8-byte elements
-  const float to_fixed = DET ? det_scale[0] : 0.0f;
+  const float to_fixed = DET ? det->to_fixed : 0.0f;
   const int red = min(lane, N - 1);     // the sum this lane reduces (lanes >= N idle along on a copy)
   const int col = Fn::column(red);      // ... and its float inside the triangle's acc row
 
@@ -543,7 +480,7 @@ __global__ __launch_bounds__(kWave, Fn::kMinWavesPerSimd) void k_accumulate_lane
   int merge_count = 0;   // slots in use, wave-uniform
   auto commit = [&](const int t, const float v) {
     if (lane < N) {
-      if (DET) atomic_add_fixed(&acc_fixed[(size_t)t * STRIDE + col], v, to_fixed, det_overflow_flag(det_scale));
+      if (DET) atomic_add_fixed(&acc_fixed[(size_t)t * STRIDE + col], v, to_fixed, det_overflow_flag(det));
       else atomicAdd(&acc_img[(size_t)t * STRIDE + col], v);
     }
   };
@@ -814,11 +751,11 @@ inline int launch_sum_strip_rows(const float *rows, int B, int per_image, int ro
   return check_launch();
 }
 
-// det_scale: nullptr = float atomics; else the device pair (2^k, 2^-k) of the deterministic mode and
-// `acc` holds 8-byte fixed-point elements.
+// det: nullptr = float atomics; else the deterministic mode's block (det_fixed.h) and `acc` holds 8-byte
+// fixed-point elements.
 template <class Fn>
 inline int launch_accumulate_rows(const Fn &fn, int B, int T, int W, int H, float *acc,
-                                  hipStream_t s, const float *det_scale = nullptr) {
+                                  hipStream_t s, const DetBlock *det = nullptr) {
   g_last_accumulate_kernel = __PRETTY_FUNCTION__;
   const int regions_x = (W + kWave - 1) / kWave;
   constexpr int kRowsRegionH = Fn::kRowsPerWave * (kRowsThreads / kWave);
@@ -826,14 +763,14 @@ inline int launch_accumulate_rows(const Fn &fn, int B, int T, int W, int H, floa
   const int per_image = regions_x * regions_y;
   const int n_regions = per_image * B;
   const int per_xcd = (n_regions + kXcds - 1) / kXcds;
-  if (det_scale)
+  if (det)
     hipLaunchKernelGGL((k_accumulate_rows<Fn, true>), dim3((unsigned)(per_xcd * kXcds)),
                        dim3(kRowsThreads), 0, s, fn, T, W, H, regions_x, per_image, n_regions,
-                       per_xcd, acc, det_scale);
+                       per_xcd, acc, det);
   else
     hipLaunchKernelGGL((k_accumulate_rows<Fn, false>), dim3((unsigned)(per_xcd * kXcds)),
                        dim3(kRowsThreads), 0, s, fn, T, W, H, regions_x, per_image, n_regions,
-                       per_xcd, acc, det_scale);
+                       per_xcd, acc, det);
   return check_launch();
 }
 
@@ -855,7 +792,7 @@ inline int lanes_strips_per_image(int B, int W, int H) {
 }
 template <class Fn>
 inline int launch_accumulate_lanes(const Fn &fn, int B, int T, int W, int H, float *acc,
-                                   hipStream_t s, const float *det_scale = nullptr) {
+                                   hipStream_t s, const DetBlock *det = nullptr) {
   g_last_accumulate_kernel = __PRETTY_FUNCTION__;
   const int rows = lanes_rows_per_wave<Fn>(B, W, H);
   const int regions_x = (W + kWave - 1) / kWave;
@@ -863,9 +800,9 @@ inline int launch_accumulate_lanes(const Fn &fn, int B, int T, int W, int H, flo
   const int per_image = regions_x * regions_y;
   const int n_regions = per_image * B;
   const int per_xcd = (n_regions + kXcds - 1) / kXcds;
-  if (det_scale) return MR_EINVAL;  // the deterministic mode stays on the rows / runs kernels (not instantiated here)
+  if (det) return MR_EINVAL;  // the deterministic mode stays on the rows / runs kernels (not instantiated here)
   hipLaunchKernelGGL((k_accumulate_lanes<Fn, false>), dim3((unsigned)(per_xcd * kXcds)), dim3(kWave), 0, s,
-                     fn, T, W, H, regions_x, per_image, n_regions, per_xcd, rows, acc, det_scale);
+                     fn, T, W, H, regions_x, per_image, n_regions, per_xcd, rows, acc, det);
   return check_launch();
 }
 
@@ -880,14 +817,14 @@ inline int launch_accumulate_runs(const Fn &fn, int B, int T, int W, int H, floa
   const int per_xcd = (n_regions + kXcds - 1) / kXcds;
   hipLaunchKernelGGL((k_accumulate_runs<Fn, false>), dim3((unsigned)(per_xcd * kXcds)),
                      dim3(kRunThreads), 0, s, fn, T, W, H, regions_x, per_image, n_regions,
-                     per_xcd, acc, (const float *)nullptr);
+                     per_xcd, acc, (const DetBlock *)nullptr);
   return check_launch();
 }
 
-// Deterministic mode: `acc` holds 8-byte fixed-point elements, det_scale = device (2^k, 2^-k).
+// Deterministic mode: `acc` holds 8-byte fixed-point elements, det = the launch's block (det_fixed.h).
 template <class Fn>
 inline int launch_accumulate_runs_fixed(const Fn &fn, int B, int T, int W, int H, float *acc,
-                                        const float *det_scale, hipStream_t s) {
+                                        const DetBlock *det, hipStream_t s) {
   g_last_accumulate_kernel = __PRETTY_FUNCTION__;
   const int regions_x = (W + kWave - 1) / kWave;
   const int regions_y = (H + kRunRegionH - 1) / kRunRegionH;
@@ -896,7 +833,7 @@ inline int launch_accumulate_runs_fixed(const Fn &fn, int B, int T, int W, int H
   const int per_xcd = (n_regions + kXcds - 1) / kXcds;
   hipLaunchKernelGGL((k_accumulate_runs<Fn, true>), dim3((unsigned)(per_xcd * kXcds)),
                      dim3(kRunThreads), 0, s, fn, T, W, H, regions_x, per_image, n_regions,
-                     per_xcd, acc, det_scale);
+                     per_xcd, acc, det);
   return check_launch();
 }
 

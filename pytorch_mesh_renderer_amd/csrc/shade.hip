@@ -672,7 +672,7 @@ __global__ __launch_bounds__(kThreads) void k_shade_scatter(
 #endif
 template <bool DET>
 __global__ __launch_bounds__(kThreads) void k_shade_gather(
-    const float *__restrict__ acc, const float *__restrict__ det_scale, const int32_t *__restrict__ offsets,
+    const float *__restrict__ acc, const DetBlock *__restrict__ det, const int32_t *__restrict__ offsets,
     const int32_t *__restrict__ entries, int B, int V, int T, float *__restrict__ dnormals,
     float *__restrict__ dpositions, float *__restrict__ ddiffuse, float *__restrict__ dclip,
     const float *__restrict__ transforms) {
@@ -702,7 +702,7 @@ __global__ __launch_bounds__(kThreads) void k_shade_gather(
         const unsigned t = (unsigned)e[u] / 3u, k = (unsigned)e[u] - 3u * t;
         const unsigned at = t * 36u + col0 + k * colk;
         // DET: fixed-point rows (8-byte elements) back to float, then the same fixed-order sums
-        val[u] = e[u] < 0 ? 0.f : DET ? (float)acc_x[at] * det_scale[1] : acc_f[at];
+        val[u] = e[u] < 0 ? 0.f : DET ? det_to_float(acc_x[at], det) : acc_f[at];
       }
 #pragma unroll
       for (int u = 0; u < kChunk; ++u) sum += val[u];
@@ -718,7 +718,7 @@ __global__ __launch_bounds__(kThreads) void k_shade_gather(
       sum += (m[0] * dx + m[4] * dy) + m[12] * dw;
     }
   }
-  if (DET && *det_overflow_flag(det_scale)) sum = __int_as_float(0x7fc00000);  // see atomic_add_fixed
+  if (DET && det->overflow) sum = det_to_float(0, det);  // also the outputs that no fixed-point sum feeds (det_fixed.h)
   if (!dclip && j >= 9) return;
   float *out = j < 3 ? dnormals + gid * 3 + j
              : j < 6 ? dpositions + gid * 3 + (j - 3)
@@ -774,15 +774,9 @@ __global__ __launch_bounds__(kThreads) void k_shade_gather_fold(
   dpositions[gid * 3 + c] = scale_src ? sum * (scale_src[0] * scale_mul) : sum;
 }
 
-inline unsigned capped_blocks(size_t n) {
-  const size_t want = (n + kThreads - 1) / kThreads;
-  const size_t cap = 256u * 32u;
-  return (unsigned)(want < cap ? (want ? want : 1) : cap);
-}
 
 // 8 bytes per element: room for the deterministic mode's fixed-point accumulators
 inline size_t shade_acc_bytes(int B, int T) { return align_up((size_t)B * T * 36 * sizeof(long long), 256); }
-constexpr size_t kDetMiscBytes = 512;  // det_scale (2 floats), max bits (1 int)
 // one row of light sums per strip of the pixel pass (the variant with light gradients walks 16-row strips)
 struct LightGradLaneGeometry { static constexpr int kLaneRowsPerWave = MR_LANE_ROWS_LG; };  // = ShadeLaneFn<..., LG = true, ...>'s strips
 inline int light_strips_per_image(int B, int W, int H, bool lanes) {
@@ -791,37 +785,6 @@ inline int light_strips_per_image(int B, int W, int H, bool lanes) {
 inline size_t light_rows_bytes(int B, int W, int H) {
   const int strips = max(light_strips_per_image(B, W, H, true), light_strips_per_image(B, W, H, false));
   return align_up((size_t)B * strips * (kMaxLights * 6 + 3) * sizeof(float), 256);
-}
-
-// ---- deterministic mode helpers -------------------------------------------------------------
-// largest |x| of an array as float bits (non-negative floats order like integers; a NaN sorts on top)
-__global__ __launch_bounds__(kThreads) void k_abs_max(const float4 *__restrict__ x, size_t n4, int *__restrict__ max_bits) {
-  int best = 0;
-  for (size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x; i < n4; i += (size_t)gridDim.x * kThreads) {
-    const float4 v = x[i];
-    best = max(max(best, __float_as_int(fabsf(v.x))), max(__float_as_int(fabsf(v.y)), __float_as_int(fabsf(v.z))));
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) best = max(best, __shfl_down(best, off));
-  // one atomic per WORKGROUP (thousands of wavefronts on one address queue up behind each other)
-  __shared__ int s_best[kThreads / kWave];
-  if ((threadIdx.x & (kWave - 1)) == 0) s_best[threadIdx.x >> 6] = best;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < kThreads / kWave; ++w) best = max(best, s_best[w]);
-    if (best != 0) atomicMax(max_bits, best);
-  }
-}
-
-// (2^k, 2^-k) with k such that the largest upstream gradient maps to about 2^41
-__global__ void k_det_scale(const int *__restrict__ max_bits, const float *__restrict__ sign_upstream,
-                            float sign_inv_n, float *__restrict__ det_scale) {
-  const float g = sign_upstream ? fabsf(sign_upstream[0] * sign_inv_n) : __int_as_float(max_bits[0]);
-  int e = 0;
-  if (g > 0.0f && g < INFINITY) (void)frexpf(g, &e);  // g = m * 2^e, m in [0.5, 1)
-  const int k = min(max(41 - e, -100), 100);
-  det_scale[0] = ldexpf(1.0f, k);
-  det_scale[1] = ldexpf(1.0f, -k);
 }
 
 inline size_t corner_bytes(int B, int T) { return align_up((size_t)B * T * sizeof(CornerRec), 256); }
@@ -869,7 +832,7 @@ size_t shade_backward_prepared_bytes(int B, int T) { return fold_prepared_bytes(
 
 size_t shade_backward_ws(int B, int V, int T, int W, int H) {
   return shade_acc_bytes(B, T) + align_up((size_t)B * T * sizeof(BwdRec), 256) + corner_bytes(B, T) +
-         kDetMiscBytes + light_rows_bytes(B, W, H) + align_up((size_t)B * T * sizeof(FoldRec), 256) +
+         kDetBlockBytes + light_rows_bytes(B, W, H) + align_up((size_t)B * T * sizeof(FoldRec), 256) +
          align_up((size_t)B * V * 4 * sizeof(float), 256);  // last two: the folded kernel's records, dclip scratch
 }
 
@@ -933,9 +896,8 @@ int launch_shade_backward(const float *drgba, const uint8_t *signs, const float 
   float *acc = (float *)ws;
   BwdRec *recs = (BwdRec *)((char *)ws + shade_acc_bytes(B, T));
   CornerRec *corners = (CornerRec *)((char *)recs + align_up((size_t)B * T * sizeof(BwdRec), 256));
-  float *det_scale = (float *)((char *)corners + corner_bytes(B, T));
-  int *max_bits = (int *)(det_scale + 4);
-  float *light_rows = (float *)((char *)det_scale + kDetMiscBytes);
+  DetBlock *det_block = (DetBlock *)((char *)corners + corner_bytes(B, T));
+  float *light_rows = (float *)((char *)det_block + kDetBlockBytes);
   FoldRec *fold_recs = (FoldRec *)((char *)light_rows + light_rows_bytes(B, W, H));
   const bool fold_diff = fold && MR_SHADE_FOLD_DIFF && (corner_records != nullptr || prepared != nullptr) && !dnormals && !ddiffuse &&
                          !light_grads;   // (with light gradients: ShadeDiffLaneFn<..., LG>, below)
@@ -958,15 +920,10 @@ int launch_shade_backward(const float *drgba, const uint8_t *signs, const float 
   if (!fused_clear && zero_async(acc, acc_bytes, s) != hipSuccess) return check_launch();
   int rc = MR_OK;
   if (det) {
-    if (zero_async(det_scale, kDetMiscBytes, s) != hipSuccess) return check_launch();
-    if (!signs) {
-      const size_t n4 = (size_t)B * H * W;
-      const unsigned blocks = capped_blocks(n4) < 2048u ? capped_blocks(n4) : 2048u;
-      hipLaunchKernelGGL(k_abs_max, dim3(blocks), dim3(kThreads), 0, s, (const float4 *)drgba, n4, max_bits);
-      if ((rc = check_launch()) != MR_OK) return rc;
-    }
-    hipLaunchKernelGGL(k_det_scale, dim3(1), dim3(1), 0, s, max_bits, sign_upstream, sign_inv_n, det_scale);
-    if ((rc = check_launch()) != MR_OK) return rc;
+    // sign codes: every upstream gradient is +-sign_upstream[0] / n; a dense image: its largest |R|, |G| or |B|
+    rc = signs ? launch_det_scale_of_scalar(sign_upstream, sign_inv_n, det_block, s)
+               : launch_det_scale(drgba, (size_t)B * H * W * 4, 1.0f, det_block, s, /*rgb_of_rgba=*/true);
+    if (rc != MR_OK) return rc;
   }
   if (use_prepared) rc = MR_OK;
   else
@@ -1103,19 +1060,19 @@ int launch_shade_backward(const float *drgba, const uint8_t *signs, const float 
     if (signs && light_grads) {                                                                 \
       ShadeGradFn<NL, true, true> fn{nullptr, signs, sign_upstream, sign_inv_n, ids, (const F3 *)bary, corners, \
                                      recs, lights, light_rows, T, W, H};                        \
-      rc = launch_accumulate_rows(fn, B, T, W, H, acc, s, det ? det_scale : nullptr);           \
+      rc = launch_accumulate_rows(fn, B, T, W, H, acc, s, det ? det_block : nullptr);           \
     } else if (signs) {                                                                         \
       ShadeGradFn<NL, true, false> fn{nullptr, signs, sign_upstream, sign_inv_n, ids, (const F3 *)bary, corners, \
                                       recs, lights, nullptr, T, W, H};                          \
-      rc = launch_accumulate_rows(fn, B, T, W, H, acc, s, det ? det_scale : nullptr);           \
+      rc = launch_accumulate_rows(fn, B, T, W, H, acc, s, det ? det_block : nullptr);           \
     } else if (light_grads) {                                                                   \
       ShadeGradFn<NL, false, true> fn{(const float4 *)drgba, nullptr, nullptr, 0.0f, ids, (const F3 *)bary, \
                                       corners, recs, lights, light_rows, T, W, H};              \
-      rc = launch_accumulate_rows(fn, B, T, W, H, acc, s, det ? det_scale : nullptr);           \
+      rc = launch_accumulate_rows(fn, B, T, W, H, acc, s, det ? det_block : nullptr);           \
     } else {                                                                                    \
       ShadeGradFn<NL, false, false> fn{(const float4 *)drgba, nullptr, nullptr, 0.0f, ids, (const F3 *)bary, \
                                        corners, recs, lights, nullptr, T, W, H};                \
-      rc = launch_accumulate_rows(fn, B, T, W, H, acc, s, det ? det_scale : nullptr);           \
+      rc = launch_accumulate_rows(fn, B, T, W, H, acc, s, det ? det_block : nullptr);           \
     }                                                                                           \
   }
   switch (L) {
@@ -1128,11 +1085,11 @@ int launch_shade_backward(const float *drgba, const uint8_t *signs, const float 
       if (signs) {
         ShadeGradFn<0, true, false> fn{nullptr, signs, sign_upstream, sign_inv_n, ids, (const F3 *)bary, corners,
                                        recs, lights, nullptr, T, W, H};
-        rc = launch_accumulate_rows(fn, B, T, W, H, acc, s, det ? det_scale : nullptr);
+        rc = launch_accumulate_rows(fn, B, T, W, H, acc, s, det ? det_block : nullptr);
       } else {
         ShadeGradFn<0, false, false> fn{(const float4 *)drgba, nullptr, nullptr, 0.0f, ids, (const F3 *)bary,
                                         corners, recs, lights, nullptr, T, W, H};
-        rc = launch_accumulate_rows(fn, B, T, W, H, acc, s, det ? det_scale : nullptr);
+        rc = launch_accumulate_rows(fn, B, T, W, H, acc, s, det ? det_block : nullptr);
       }
     } break;
   }
@@ -1160,10 +1117,10 @@ int launch_shade_backward(const float *drgba, const uint8_t *signs, const float 
     const long nbv = (long)B * V * 16;  // sixteen lanes per vertex
     const dim3 grid((unsigned)((nbv + kThreads - 1) / kThreads));
     if (det) {
-      hipLaunchKernelGGL(k_shade_gather<true>, grid, dim3(kThreads), 0, s, acc, det_scale, vertex_offsets,
+      hipLaunchKernelGGL(k_shade_gather<true>, grid, dim3(kThreads), 0, s, acc, det_block, vertex_offsets,
                          vertex_entries, B, V, T, dnormals, dpositions, ddiffuse, dclip, transforms);
     } else {
-      hipLaunchKernelGGL(k_shade_gather<false>, grid, dim3(kThreads), 0, s, acc, det_scale, vertex_offsets,
+      hipLaunchKernelGGL(k_shade_gather<false>, grid, dim3(kThreads), 0, s, acc, det_block, vertex_offsets,
                          vertex_entries, B, V, T, dnormals, dpositions, ddiffuse, dclip, transforms);
     }
     return check_launch();

@@ -1079,10 +1079,10 @@ __global__ __launch_bounds__(kThreads) void k_spec_scatter(
 // Vertex-centric alternative (round 3; the diffuse path has had it since round 2): sixteen lanes per
 // (image, vertex), one per output float -- A attribute gradients, then the three clip gradients -- sum the
 // rows of the incident triangles over the CSR adjacency (entry = 3 * triangle + corner).  No atomics,
-// every output written exactly once, fixed order; DET: the rows hold 64-bit fixed point (run_accum.h).
+// every output written exactly once, fixed order; DET: the rows hold 64-bit fixed point (det_fixed.h).
 template <int A, bool DET>
 __global__ __launch_bounds__(kThreads) void k_spec_gather(
-    const float *__restrict__ acc, const float *__restrict__ det_scale, const int32_t *__restrict__ offsets,
+    const float *__restrict__ acc, const DetBlock *__restrict__ det, const int32_t *__restrict__ offsets,
     const int32_t *__restrict__ entries, int B, int V, int T, float *__restrict__ dnormals,
     float *__restrict__ dpositions, float *__restrict__ ddiffuse, float *__restrict__ dspecular,
     float *__restrict__ dshininess, float *__restrict__ dclip) {
@@ -1109,13 +1109,13 @@ __global__ __launch_bounds__(kThreads) void k_spec_gather(
       for (int u = 0; u < kChunk; ++u) {
         const unsigned t = (unsigned)e[u] / 3u, k = (unsigned)e[u] - 3u * t;
         const unsigned at = t * 48u + col0 + k * colk;
-        val[u] = e[u] < 0 ? 0.f : DET ? (float)acc_x[at] * det_scale[1] : acc_f[at];
+        val[u] = e[u] < 0 ? 0.f : DET ? det_to_float(acc_x[at], det) : acc_f[at];
       }
 #pragma unroll
       for (int u = 0; u < kChunk; ++u) sum += val[u];
     }
   }
-  if (DET && *det_overflow_flag(det_scale)) sum = __int_as_float(0x7fc00000);  // see atomic_add_fixed
+  if (DET && det->overflow) sum = det_to_float(0, det);  // also a vertex that no fixed-point sum feeds (det_fixed.h)
   float *out = j < 3 ? dnormals + gid * 3 + j
              : j < 6 ? dpositions + gid * 3 + (j - 3)
              : j < 9 ? ddiffuse + gid * 3 + (j - 6)
@@ -1247,7 +1247,7 @@ int spec_backward(const float *drgba, const uint8_t *signs, const float *sign_up
   p += spec_partials_bytes(B, W, H);
   float *light_rows = (float *)p;
   p += spec_light_rows_bytes(B, W, H);
-  float *det_block = (float *)p;
+  DetBlock *det_block = (DetBlock *)p;
   p += kDetBlockBytes;
   SpecFoldRec<A> *fold_recs = (SpecFoldRec<A> *)p;
   if (zero_async(acc, (size_t)B * T * 48 * (det ? sizeof(long long) : sizeof(float)), s) != hipSuccess)

@@ -433,7 +433,7 @@ constexpr int kLightRow = 16;  // floats per wavefront row of light sums (4 x kM
 #endif
 // DET (mr_set_deterministic, round 3): the 39 sums of a (wavefront, triangle) leave as 64-bit fixed-point
 // integer atomics into int64 copies of the four outputs (det_fixed: dclip [B,V,4], then dnormals,
-// dpositions, ddiffuse [B,V,3] each) instead of float atomics into the outputs; k_soft_from_fixed converts.
+// dpositions, ddiffuse [B,V,3] each) instead of float atomics into the outputs; launch_det_to_float converts.
 template <bool DET, int ML>
 __global__ __launch_bounds__(kThreads, MR_SOFT_BWD_WAVES) void k_soft_backward(
     const SoftRec *__restrict__ recs, const CornerRec *__restrict__ corners,
@@ -443,7 +443,7 @@ __global__ __launch_bounds__(kThreads, MR_SOFT_BWD_WAVES) void k_soft_backward(
     int cells_per_image, const float4 *__restrict__ drgba, const float4 *__restrict__ rgba,
     const float4 *__restrict__ aux, float *__restrict__ dclip, float *__restrict__ dnormals,
     float *__restrict__ dpositions, float *__restrict__ ddiffuse, float *__restrict__ light_rows,
-    long long *__restrict__ det_fixed, const float *__restrict__ det_scale, int B) {
+    long long *__restrict__ det_fixed, const DetBlock *__restrict__ det, int B) {
   __shared__ int s_list[kListCap];
   __shared__ int s_wave_count[kThreads / 64];
   TileGeom g;
@@ -476,7 +476,7 @@ __global__ __launch_bounds__(kThreads, MR_SOFT_BWD_WAVES) void k_soft_backward(
   const size_t bv = (size_t)B * V;
   long long *fixed_base = !DET ? nullptr
                         : o_comp < 4 ? det_fixed : det_fixed + bv * 4 + (size_t)(o_comp < 7 ? 0 : (o_comp < 10 ? 1 : 2)) * bv * 3;
-  const float to_fixed = DET ? det_scale[0] : 0.0f;
+  const float to_fixed = DET ? det->to_fixed : 0.0f;
 
   float4 go = make_float4(0.f, 0.f, 0.f, 0.f), out = go, ax = make_float4(0.f, 1.f, 1.f, 0.f);
   if (g.in_image) {
@@ -683,7 +683,7 @@ __global__ __launch_bounds__(kThreads, MR_SOFT_BWD_WAVES) void k_soft_backward(
         __builtin_amdgcn_wave_barrier();  // the next candidate overwrites the rows
         if (lane < 39 && sum != 0.0f && (unsigned)my_vertex < (unsigned)V) {
           const size_t at = ((size_t)g.img * V + my_vertex) * out_stride + out_off;
-          if (DET) atomic_add_fixed(fixed_base + at, sum, to_fixed, det_overflow_flag(det_scale));
+          if (DET) atomic_add_fixed(fixed_base + at, sum, to_fixed, det_overflow_flag(det));
           else atomicAdd(out_base + at, sum);
         }
       }
@@ -741,19 +741,7 @@ __global__ __launch_bounds__(kLightSumThreads) void k_soft_light_sum(const float
   }
 }
 
-// DET: the int64 sums back to float, array by array (dclip [B,V,4] | dnormals | dpositions | ddiffuse [B,V,3])
-__global__ __launch_bounds__(kThreads) void k_soft_from_fixed(const long long *__restrict__ fixed,
-                                                             const float *__restrict__ det_scale, size_t bv,
-                                                             float *__restrict__ dclip, float *__restrict__ dnormals,
-                                                             float *__restrict__ dpositions, float *__restrict__ ddiffuse) {
-  const size_t i = (size_t)blockIdx.x * kThreads + threadIdx.x;
-  if (i >= bv * 13) return;
-  const float v = *det_overflow_flag(det_scale) ? __int_as_float(0x7fc00000) : (float)fixed[i] * det_scale[1];
-  if (i < bv * 4) dclip[i] = v;
-  else if (i < bv * 7) dnormals[i - bv * 4] = v;
-  else if (i < bv * 10) dpositions[i - bv * 7] = v;
-  else ddiffuse[i - bv * 10] = v;
-}
+// DET: the int64 copies of the outputs, back to back: dclip [B,V,4] | dnormals | dpositions | ddiffuse [B,V,3]
 inline size_t soft_fixed_bytes(int B, int V) { return align_up((size_t)B * V * 13 * sizeof(long long), 256); }
 
 inline size_t soft_rec_bytes(int B, int T) { return align_up((size_t)B * T * sizeof(SoftRec), 256); }
@@ -913,7 +901,7 @@ int launch_soft_backward(const float *drgba, const float *rgba, const float *aux
   const SoftParams pr = soft_params(sigma, gamma, blur);
   float *light_rows = (float *)((char *)ws + soft_prepared_bytes(B, V, T, W, H));
   long long *det_fixed = (long long *)((char *)light_rows + soft_light_rows_bytes(B, W, H));
-  float *det_block = (float *)((char *)det_fixed + soft_fixed_bytes(B, V));
+  DetBlock *det_block = (DetBlock *)((char *)det_fixed + soft_fixed_bytes(B, V));
 #define MR_SOFT_BWD(DET_, ML_)                                                                              \
   hipLaunchKernelGGL((k_soft_backward<DET_, ML_>), dim3((unsigned)(tg.per_xcd * kXcds)), dim3(kThreads), 0, s, \
                      recs, corners, lpos, lint, tris, V, T, W, H, L, pr, tg.tiles_x, tg.per_image, tg.n_tiles,  \
@@ -938,10 +926,9 @@ int launch_soft_backward(const float *drgba, const float *rgba, const float *aux
   const int rc2 = check_launch();
   if (rc2 != MR_OK) return rc2;
   if (det) {
-    const size_t n = (size_t)B * V * 13;
-    hipLaunchKernelGGL(k_soft_from_fixed, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, s,
-                       det_fixed, det_block, (size_t)B * V, dclip, dnormals, dpositions, ddiffuse);
-    const int rc3 = check_launch();
+    const size_t bv = (size_t)B * V;
+    const int rc3 = launch_det_to_float(det_fixed, det_block,
+                                        DetSegments{{dclip, dnormals, dpositions, ddiffuse}, {bv * 4, bv * 3, bv * 3, bv * 3}}, s);
     if (rc3 != MR_OK) return rc3;
   }
   hipLaunchKernelGGL(k_soft_light_sum, dim3((unsigned)B), dim3(kLightSumThreads), 0, s, light_rows,

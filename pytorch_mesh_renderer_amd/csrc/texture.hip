@@ -19,7 +19,7 @@
 // with one global atomic per lane and channel.  Deterministic mode (mr_set_deterministic) accumulates 64-bit fixed
 // point in LDS and in the workspace (integer adds are order-independent) and converts at the end, NaN on overflow.
 #include "mr_internal.h"
-#include "run_accum.h"
+#include "det_fixed.h"
 
 namespace mr {
 
@@ -160,7 +160,7 @@ __device__ __forceinline__ float wave_sum_f(float v) {
   return v;
 }
 
-// one contribution into the LDS window: float add, or fixed point (run_accum.h's rule, LDS u64 adds)
+// one contribution into the LDS window: float add, or fixed point (det_fixed.h's rule, LDS u64 adds)
 template <int MODE>
 __device__ __forceinline__ void window_add(unsigned long long *win, int k, float v, float to_fixed, int *overflow) {
   if (MODE == kModeFloat) {
@@ -187,7 +187,7 @@ __global__ __launch_bounds__(kTexThreads) void k_tex_backward(TexArgs a, int til
                                                              float *__restrict__ dtex,
                                                              unsigned long long *__restrict__ dtex_fixed,
                                                              float2 *__restrict__ duv,
-                                                             float *__restrict__ det_block) {
+                                                             DetBlock *__restrict__ det_block) {
   __shared__ unsigned long long window[kWindowBytes / 8];
   __shared__ int box_part[kTexThreads / kWave][4];
   const int b = (int)blockIdx.y;
@@ -263,8 +263,8 @@ __global__ __launch_bounds__(kTexThreads) void k_tex_backward(TexArgs a, int til
   }
   if (bx0 > bx1) return;  // nothing sampled in the tile (uniform)
 
-  const float to_fixed = MODE == kModeFixed ? det_block[0] : 0.0f;
-  int *overflow = MODE == kModeFixed ? det_overflow_flag(det_block) : nullptr;
+  const float to_fixed = MODE == kModeFixed ? det_block->to_fixed : 0.0f;
+  int *overflow = MODE == kModeFixed ? &det_block->overflow : nullptr;
   const int bw = bx1 - bx0 + 1, bh = by1 - by0 + 1;  // >= 1 each (1 under clamp with Wt or Ht = 1), < 2^26
   constexpr int kCap = MODE == kModeFixed ? kWindowBytes / 8 : kWindowBytes / 4;
   if ((long long)bw * bh * C <= kCap) {
@@ -365,16 +365,6 @@ __global__ __launch_bounds__(kTexThreads) void k_tex_backward(TexArgs a, int til
   }
 }
 
-__global__ __launch_bounds__(256) void k_tex_from_fixed(const long long *__restrict__ fixed,
-                                                        const float *__restrict__ det_block, size_t n,
-                                                        float *__restrict__ out) {
-  // a contribution did not fit the fixed-point range (run_accum.h, atomic_add_fixed): NaN, not garbage
-  const bool bad = *det_overflow_flag(det_block) != 0;
-  const float back = det_block[1];
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256)
-    out[i] = bad ? __int_as_float(0x7fc00000) : (float)fixed[i] * back;
-}
-
 inline size_t tex_floats(int tex_batched, int Ht, int Wt, int C, int B) {
   return (size_t)(tex_batched ? B : 1) * Ht * Wt * C;
 }
@@ -392,7 +382,7 @@ int launch_forward_c(const TexArgs &a, int B, int boundary, float *out, hipStrea
 
 template <int C, int MODE>
 int launch_backward_c(const TexArgs &a, int B, int boundary, const float *dout, float *dtex,
-                      unsigned long long *dtex_fixed, float *duv, float *det_block, hipStream_t s) {
+                      unsigned long long *dtex_fixed, float *duv, DetBlock *det_block, hipStream_t s) {
   const int tiles_x = (a.W + kTileW - 1) / kTileW, tiles_y = (a.H + kTileH - 1) / kTileH;
   const dim3 grid((unsigned)((size_t)tiles_x * tiles_y), (unsigned)B), block(kTexThreads);
   if (boundary == MR_TEXTURE_WRAP)
@@ -406,7 +396,7 @@ int launch_backward_c(const TexArgs &a, int B, int boundary, const float *dout, 
 
 template <int MODE>
 int launch_backward_mode(const TexArgs &a, int C, int B, int boundary, const float *dout, float *dtex,
-                         unsigned long long *dtex_fixed, float *duv, float *det_block, hipStream_t s) {
+                         unsigned long long *dtex_fixed, float *duv, DetBlock *det_block, hipStream_t s) {
   switch (C) {
     case 1: return launch_backward_c<1, MODE>(a, B, boundary, dout, dtex, dtex_fixed, duv, det_block, s);
     case 2: return launch_backward_c<2, MODE>(a, B, boundary, dout, dtex, dtex_fixed, duv, det_block, s);
@@ -453,7 +443,7 @@ int launch_texture_backward(const float *dout, const float *tex, int tex_batched
   // Deterministic: the scale comes from the largest |dout| (every contribution is w * dout with w <= 1) and the
   // number of pixels that sample one texture, so that no texel's sum can leave the 64-bit range.
   unsigned long long *fixed = (unsigned long long *)ws;
-  float *det_block = (float *)((char *)ws + fixed_bytes(tex_batched, Ht, Wt, C, B));
+  DetBlock *det_block = (DetBlock *)((char *)ws + fixed_bytes(tex_batched, Ht, Wt, C, B));
   if (zero_async(fixed, fixed_bytes(tex_batched, Ht, Wt, C, B), s) != hipSuccess) return check_launch();
   const double per_texture = (double)(tex_batched ? 1 : B) * W * H;
   const float gain = (float)fmax(1.0, per_texture / (double)(1 << 21));
@@ -461,10 +451,7 @@ int launch_texture_backward(const float *dout, const float *tex, int tex_batched
   if (rc != MR_OK) return rc;
   rc = launch_backward_mode<kModeFixed>(a, C, B, boundary, dout, nullptr, fixed, duv, det_block, s);
   if (rc != MR_OK) return rc;
-  const size_t want = (n_tex + 255) / 256;
-  hipLaunchKernelGGL(k_tex_from_fixed, dim3((unsigned)(want < 4096 ? want : 4096)), dim3(256), 0, s,
-                     (const long long *)fixed, (const float *)det_block, n_tex, dtex);
-  return check_launch();
+  return launch_det_to_float((const long long *)fixed, det_block, dtex, n_tex, s);
 }
 
 }  // namespace mr

@@ -168,6 +168,16 @@ def test_deterministic_mode_reproduces_dclip_bit_for_bit():
     before = _native.set_deterministic(True)
     try:
         runs = [_native.antialias_backward(dout, image, ids, bary, z, clip, tris, opp) for _ in range(2)]
+        # a contribution outside the fixed-point range (csrc/det_fixed.h) -- an infinite upstream gradient on one
+        # pixel that a blended pair modifies, and a NaN -- poisons the whole of dclip (dimage is written per pixel)
+        pair_mask = _native.antialias_forward(image, ids, bary, z, clip, tris, opp, want_pair_mask=True)[1]
+        blended = (pair_mask != 0).nonzero()
+        b, y, x = [int(t) for t in blended[len(blended) // 2]]
+        for poison in (float("inf"), float("nan")):
+            bad = dout.clone()
+            bad[b, y, x, 1] = poison
+            poisoned = _native.antialias_backward(bad, image, ids, bary, z, clip, tris, opp)[1]
+            assert not bool(torch.isfinite(poisoned).any()), poison
     finally:
         _native.set_deterministic(before)
     assert torch.equal(runs[0][1], runs[1][1]) and torch.equal(runs[0][0], runs[1][0])

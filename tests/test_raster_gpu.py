@@ -616,6 +616,64 @@ def test_deterministic_mode_flags_contributions_outside_its_fixed_point_range(de
     floaty[0, y, x, 1] = float("inf")
     assert not bool(torch.isfinite(_native.rasterize_backward(floaty, clip, tris, ids, bary)).all())
 
+    # The same policy in the other per-triangle passes that share the format (csrc/det_fixed.h): the diffuse and the
+    # specular shading backward of render() under a dense upstream gradient, and the fused interpolation backward of
+    # rasterize_clip_space() on this G-buffer.  Only outputs that are accumulated in fixed point are looked at (not
+    # the light gradients: fixed-order row sums).  In range, the deterministic kernels agree with the float-atomic
+    # ones within the parity tolerance of test_deterministic_mode_covers_specular_and_rasterize_backward.
+    from pytorch_mesh_renderer_amd import mesh_renderer
+    from pytorch_mesh_renderer_amd.common import shapes
+    from pytorch_mesh_renderer_amd.mesh_renderer.rasterize import rasterize_clip_space
+    gen = torch.Generator().manual_seed(23)
+    vertices, cube_tris, normals = shapes.cube(2.0)
+    cube_tris = torch.flip(cube_tris, [1]).contiguous().to(device)
+    eye = torch.tensor([[2.0, 3.0, 6.0]], device=device)
+    base = {"vertices": vertices.unsqueeze(0), "normals": normals.unsqueeze(0), "diffuse": torch.rand(1, 8, 3, generator=gen),
+            "specular": torch.rand(1, 8, 3, generator=gen), "shininess": 0.3 + torch.rand(1, 8, generator=gen)}
+    attrs = torch.rand(1, 8, 7, generator=gen)
+
+    def render_backward(specular):
+        def run(upstream):
+            names = sorted(base) if specular else ["diffuse", "normals", "vertices"]
+            leaves = {k: base[k].clone().to(device).requires_grad_(True) for k in names}
+            extra = dict(specular_colors=leaves["specular"], shininess_coefficients=leaves["shininess"]) if specular else {}
+            img = mesh_renderer.render(leaves["vertices"], cube_tris, leaves["normals"], leaves["diffuse"], eye,
+                                       torch.zeros(1, 3, device=device), torch.tensor([[0.0, 1.0, 0.0]], device=device),
+                                       eye.unsqueeze(1), torch.ones(1, 1, 3, device=device), 64, 64, **extra)
+            img.backward(upstream)
+            return img.detach(), [leaves[k].grad for k in names]
+        return run
+
+    def interp_backward(upstream):
+        c = clip.clone().requires_grad_(True)
+        a = attrs.clone().to(device).requires_grad_(True)
+        out = rasterize_clip_space(c, a, tris, 64, 64, torch.zeros(7, device=device))
+        out.backward(upstream)
+        # column z of the clip-space gradient is written as a constant 0, not summed
+        assert bool((c.grad[..., 2] == 0).all())
+        return (bary.sum(-1, keepdim=True) > 0.5).float(), [c.grad[..., [0, 1, 3]], a.grad]
+
+    for name, run, channels in (("diffuse", render_backward(False), 4), ("specular", render_backward(True), 4),
+                                ("interpolation", interp_backward, 7)):
+        upstream = (torch.randn(1, 64, 64, channels, generator=gen) / (64 * 64)).to(device)
+        image, want = run(upstream)
+        lit = (image[..., -1] > 0.5).nonzero()          # covered pixels, in the orientation of the upstream gradient
+        _, y, x = [int(t) for t in lit[len(lit) // 2]]
+        before = _native.set_deterministic(True)
+        try:
+            _, fine = run(upstream)
+            for i, (a, d) in enumerate(zip(fine, want)):
+                scale = float(d.abs().max())
+                np.testing.assert_allclose(a.cpu().numpy(), d.cpu().numpy(), atol=max(1e-4 * scale, 1e-9), rtol=1e-3,
+                                           err_msg="%s, output %d" % (name, i))
+            for poison in (float("inf"), float("nan")):
+                bad = upstream.clone()
+                bad[0, y, x, 1] = poison
+                for i, got in enumerate(run(bad)[1]):
+                    assert not bool(torch.isfinite(got).any()), (name, i, poison)
+        finally:
+            _native.set_deterministic(before)
+
 
 def test_rasterize_triangles_cpp_shim_is_a_drop_in(device):
     """`import rasterize_triangles_cpp` + the exact call sequence of the reference's

@@ -144,7 +144,7 @@ def test_soft_backward_deterministic_mode_is_bit_reproducible(device):
     tris = job["triangles"].to(device)
     w = torch.rand(2, 128, 128, 4, generator=torch.Generator().manual_seed(3)).to(device) / (128 * 128)
 
-    def run():
+    def run(w=w):
         leaves = {k: job[k].clone().to(device).requires_grad_(True) for k in ("vertices", "diffuse", "light_positions")}
         img = soft_mesh_renderer.render(leaves["vertices"], tris, leaves["diffuse"], job["eyes"].to(device),
                                         torch.zeros(2, 3, device=device), torch.tensor([0.0, 1.0, 0.0], device=device),
@@ -156,6 +156,14 @@ def test_soft_backward_deterministic_mode_is_bit_reproducible(device):
     before = _native.set_deterministic(True)
     try:
         first, second = run(), run()
+        # a contribution outside the fixed-point range (csrc/det_fixed.h) -- an infinite upstream gradient on one
+        # pixel inside the silhouette, and a NaN -- poisons every output that is accumulated in fixed point (the
+        # vertex and diffuse gradients; the light gradient is a fixed-order sum of float rows)
+        for poison in (float("inf"), float("nan")):
+            bad = w.clone()
+            bad[0, 64, 64, 1] = poison
+            d_diffuse, _, d_vertices = run(bad)
+            assert not bool(torch.isfinite(d_diffuse).any()) and not bool(torch.isfinite(d_vertices).any()), poison
     finally:
         _native.set_deterministic(before)
     for i, (a, b, d) in enumerate(zip(first, second, default)):

@@ -217,6 +217,12 @@ def test_deterministic_texture_gradient_is_bit_identical_and_matches(Ht, Wt, bou
     before = _native.set_deterministic(True)
     try:
         runs = [_native.texture_backward(dout, tex, uv, None, boundary) for _ in range(2)]
+        # a contribution outside the fixed-point range (csrc/det_fixed.h) -- an infinite upstream gradient on one
+        # pixel of the smooth half, whose UV is valid, and a NaN -- poisons the whole of dtex (d uv is per pixel)
+        for poison in (float("inf"), float("nan")):
+            bad = dout.clone()
+            bad[1, 10, 10, 1] = poison
+            assert not bool(torch.isfinite(_native.texture_backward(bad, tex, uv, None, boundary)[0]).any()), poison
     finally:
         _native.set_deterministic(before)
     assert _native.deterministic() == before
@@ -225,7 +231,7 @@ def test_deterministic_texture_gradient_is_bit_identical_and_matches(Ht, Wt, bou
     _, dtex, _, abs_sum = ref.sample(tex, uv, None, boundary, dout)
     err = (float_dtex.double() - dtex).abs()
     assert bool((err <= 1e-5 * abs_sum).all()), float((err - 1e-5 * abs_sum).max())
-    # fixed point (run_accum.h): each contribution is rounded to the quantum 2^-k, where 2^k maps the largest |dout|
+    # fixed point (csrc/det_fixed.h): each contribution is rounded to the quantum 2^-k, where 2^k maps the largest |dout|
     # (times max(1, pixels per texture / 2^21)) into [2^40, 2^41): half a quantum of absolute error per contribution
     gain = max(1.0, B * H * W / 2.0 ** 21)
     k = min(max(41 - math.frexp(float(dout.abs().max()) * gain)[1], -100), 100)
