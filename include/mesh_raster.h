@@ -584,6 +584,48 @@ int mr_texture_backward(const float *dout, const float *tex, const float *uv, co
                         int Ht, int Wt, int C, int B, int W, int H, int boundary, float *dtex, float *duv,
                         void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- mipmapped trilinear texture mapping (no reference counterpart) ----------------------
+ * The same lookup, prefiltered ("Texture mapping").  Pyramid: level 0 is tex; level l + 1 exists
+ * while both extents of level l are even, L = 1 + min(tz(Ht), tz(Wt), max_level) levels (tz: trailing zero bits;
+ * max_level < 0: no cap; L <= 17), its texel fl(fl(fl(a + b) + fl(c + d)) * 0.25f) of the 2 x 2 block (2i,2j)
+ * (2i,2j+1) (2i+1,2j) (2i+1,2j+1) below, per channel; one pyramid per image for a batched texture.
+ * mr_texture_mip_levels reports L (0 for extents outside 1 .. 65536).
+ *   uv_da       [B,H,W,4] f32, 16-byte aligned: (du/dX, du/dY, dv/dX, dv/dY) per step of one output pixel
+ *   pyramid     levels >= 1, packed, mr_texture_mip_pyramid_bytes() bytes, 16-byte aligned (may be NULL when that
+ *               is 0): written by the forward, read by the backward
+ * ax^2 = (du/dX Wt)^2 + (dv/dX Ht)^2, ay^2 likewise with d/dY, lod = 0.5f * log2f(max(ax^2, ay^2)), 0 when a
+ * derivative is NaN, clamped to [0, L - 1]; l0 = floor(lod), f = lod - l0.  The value is the bilinear rule above at
+ * level l0 with that level's extents, and, when f > 0, (1 - f) times it plus f times the same at level l0 + 1.  The
+ * skip rule is the bilinear one, evaluated at level 0.  With uv_da all zero the output equals mr_texture_forward's
+ * bit for bit.
+ * Backward: duv is the level-weighted sum of the two levels' bilinear derivatives; dtex scatters (level weight x tap
+ * weight x dout) into a gradient pyramid (float atomics, or 64-bit fixed point under mr_set_deterministic(1)) and
+ * folds it coarsest level first, dlevel_l[i,j] += 0.25f dlevel_{l+1}[i/2,j/2], gathered; level 0 is dtex.  uv_da and
+ * mask get no gradient.  The workspace (gradient pyramid; fixed-point copy) is needed whenever dtex is wanted. */
+int mr_texture_mip_levels(int Ht, int Wt, int max_level);
+size_t mr_texture_mip_pyramid_bytes(int tex_batched, int Ht, int Wt, int C, int B, int max_level);
+int mr_texture_mip_forward(const float *tex, const float *uv, const float *uv_da, const float *mask, int tex_batched,
+                           int Ht, int Wt, int C, int B, int W, int H, int boundary, int max_level, float *pyramid,
+                           float *out, void *stream);
+size_t mr_texture_mip_backward_workspace_bytes(int tex_batched, int Ht, int Wt, int C, int B, int W, int H,
+                                               int max_level);
+int mr_texture_mip_backward(const float *dout, const float *tex, const float *pyramid, const float *uv,
+                            const float *uv_da, const float *mask, int tex_batched, int Ht, int Wt, int C, int B,
+                            int W, int H, int boundary, int max_level, float *dtex, float *duv, void *workspace,
+                            size_t workspace_bytes, void *stream);
+
+/* ---- screen-space attribute derivatives (forward only) -----------------------------------
+ * out [B,H,W,A,2] f32 (8-byte aligned), 1 <= A <= 4: (d a / d X, d a / d Y) of the perspective-correct
+ * interpolation of attributes [B,Va,A] per step of one pixel column (X) / row (Y) of the G-buffer, from the
+ * rasterizer's edge functions: with b_i = e_i / s, e_i = U[3i] px + U[3i+1] py + U[3i+2], s = e0 + e1 + e2,
+ *   d a / d X = (2 / W) sum_i a_i (U[3i] - b_i (U[0] + U[3] + U[6])) / s      (d / d Y: U[3i+1], 2 / H).
+ * Corner values are read through attribute_triangles [T,3] when given (per-corner attributes), else through
+ * triangles (then Va = V).  Background pixels (sum of barycentrics not positive) are 0.  clip 16-byte aligned.
+ * For A = 2 the output viewed as [B,H,W,4] is mr_texture_mip_forward's uv_da. */
+int mr_attribute_derivatives(const int32_t *ids, const float *bary, const float *clip, const int32_t *triangles,
+                             const float *attributes, const int32_t *attribute_triangles, int B, int V, int T,
+                             int Va, int W, int H, int A, float *out, void *stream);
+
 /* ---- mesh regularisers (no reference counterpart in the library; the reference's example7b.py has two) ----
  * Uniform Laplacian, edge length and normal consistency of a batch of meshes that share one topology
  * ("Mesh regularisers"), per image b:
@@ -668,7 +710,7 @@ int mr_tone_map(const float *image, int B, size_t elements_per_image, float gamm
  * number.  mr_soft_backward is covered as well (fixed-point integer atomics into 64-bit copies of its
  * four vertex outputs, scaled for the 1 / sigma and 1 / gamma its contributions carry; its light
  * gradients are fixed-order sums in either mode).  mr_antialias_backward is covered (fixed-point integer atomics for dclip, scaled from a first pass that finds
- * its largest per-vertex contribution).  mr_sh_shade_backward has no atomics and is bit-reproducible in either mode, and so are mr_mesh_regularizer_forward / _backward.  mr_texture_backward is covered (fixed-point integer adds, in LDS and in the workspace, for dtex, scaled from a first pass that finds the largest upstream gradient and from the number of pixels that sample one texture; duv is per pixel in either mode).  Not covered, float atomics remain: the composed
+ * its largest per-vertex contribution).  mr_sh_shade_backward has no atomics and is bit-reproducible in either mode, and so are mr_mesh_regularizer_forward / _backward.  mr_texture_backward is covered (fixed-point integer adds, in LDS and in the workspace, for dtex, scaled from a first pass that finds the largest upstream gradient and from the number of pixels that sample one texture; duv is per pixel in either mode), and so is mr_texture_mip_backward (the same fixed-point scatter into every level of the gradient pyramid, the same scale rule -- a contribution is level weight x tap weight x dout, at most |dout| -- then one gathered pass that converts each level's sums and folds them in a fixed order).  mr_texture_mip_forward and mr_attribute_derivatives have no atomics.  Not covered, float atomics remain: the composed
  * interpolation backward (mr_interpolate_backward, the path for more than 16 attributes).  mr_l1_loss_forward is always deterministic.  Returns the previous setting. */
 int mr_set_deterministic(int on);
 

@@ -272,6 +272,18 @@ def lib():
             L.mr_texture_backward_workspace_bytes.restype = sz
             L.mr_texture_backward.argtypes = [vp] * 4 + [ci] * 8 + [vp, vp, vp, sz, vp]
             L.mr_texture_backward.restype = ci
+            L.mr_texture_mip_levels.argtypes = [ci] * 3
+            L.mr_texture_mip_levels.restype = ci
+            L.mr_texture_mip_pyramid_bytes.argtypes = [ci] * 6
+            L.mr_texture_mip_pyramid_bytes.restype = sz
+            L.mr_texture_mip_forward.argtypes = [vp] * 4 + [ci] * 9 + [vp, vp, vp]
+            L.mr_texture_mip_forward.restype = ci
+            L.mr_texture_mip_backward_workspace_bytes.argtypes = [ci] * 8
+            L.mr_texture_mip_backward_workspace_bytes.restype = sz
+            L.mr_texture_mip_backward.argtypes = [vp] * 6 + [ci] * 9 + [vp, vp, vp, sz, vp]
+            L.mr_texture_mip_backward.restype = ci
+            L.mr_attribute_derivatives.argtypes = [vp] * 6 + [ci] * 7 + [vp, vp]
+            L.mr_attribute_derivatives.restype = ci
         except AttributeError as e:   # the texture entry points came without an ABI version bump
             raise NativeLibraryError("%s lacks the texture entry points (%s): rebuild it (make -C "
                                      "pytorch_mesh_renderer_amd/csrc)" % (LIB_PATH, e))
@@ -1138,6 +1150,130 @@ def texture_backward(dout, tex, uv, mask=None, boundary_mode="wrap", want_tex=Tr
                                    boundary, _ptr(dtex), _ptr(duv), _ptr(ws), have, _stream(dev))
     _check(rc, "mr_texture_backward")
     return dtex, duv
+
+
+def _max_level_code(max_mip_level):
+    """None -> -1 (no cap); otherwise a non-negative integer."""
+    if max_mip_level is None:
+        return -1
+    if isinstance(max_mip_level, bool) or not isinstance(max_mip_level, int) or max_mip_level < 0:
+        raise ValueError("max_mip_level must be None or a non-negative integer, got %r" % (max_mip_level,))
+    return min(max_mip_level, 64)
+
+
+def texture_mip_levels(Ht, Wt, max_mip_level=None):
+    """The number of pyramid levels of an Ht x Wt texture: 1 + min(tz(Ht), tz(Wt), max_mip_level).  Needs no GPU."""
+    if not (1 <= Ht <= 65536 and 1 <= Wt <= 65536):
+        raise ValueError("texture extents must be in 1 .. 65536, got %r x %r" % (Ht, Wt))
+    return lib().mr_texture_mip_levels(int(Ht), int(Wt), _max_level_code(max_mip_level))
+
+
+def _chk_texture_mip(tex, uv, uv_da, mask, boundary_mode, max_mip_level):
+    out = _chk_texture(tex, uv, mask, boundary_mode)
+    B, H, W = out[:3]
+    _chk("uv_da", uv_da, _F32, B, H, W, 4)
+    return out + (_max_level_code(max_mip_level),)
+
+
+def _mip_pyramid_views(pyramid, tex, levels):
+    """The packed pyramid buffer as a list of [Bt,Hl,Wl,C] views, levels 1 .. L-1."""
+    Ht, Wt, C = tex.shape[-3:]
+    count = tex.shape[0] if tex.dim() == 4 else 1
+    per = pyramid.view(count, -1) if pyramid.numel() else pyramid
+    out, off = [], 0
+    for l in range(1, levels):
+        h, w = Ht >> l, Wt >> l
+        out.append(per[:, off * C:(off + h * w) * C].reshape(count, h, w, C))
+        off += h * w
+    return out
+
+
+def texture_mip_forward(tex, uv, uv_da, mask=None, boundary_mode="wrap", max_mip_level=None):
+    """tex [Ht,Wt,C] or [B,Ht,Wt,C] f32, uv [B,H,W,2], uv_da [B,H,W,4] f32, mask [B,H,W] f32 or None ->
+    (out [B,H,W,C], pyramid): mipmapped trilinear samples ("Texture mapping") and the packed
+    pyramid levels >= 1 (a flat float32 tensor, empty when there is one level) that texture_mip_backward reads."""
+    B, H, W, Ht, Wt, C, batched, boundary, cap = _chk_texture_mip(tex, uv, uv_da, mask, boundary_mode, max_mip_level)
+    dev = _require_device(*[t for t in (tex, uv, uv_da, mask) if t is not None])
+    L = lib()
+    tex, uv, uv_da = _aligned16(tex.contiguous()), _aligned16(uv.contiguous()), _aligned16(uv_da.contiguous())
+    mask = mask.contiguous() if mask is not None else None
+    out = torch.empty(B, H, W, C, dtype=_F32, device=dev)
+    pyramid = torch.empty(L.mr_texture_mip_pyramid_bytes(batched, Ht, Wt, C, B, cap) // 4, dtype=_F32, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.mr_texture_mip_forward(_ptr(tex), _ptr(uv), _ptr(uv_da), _ptr(mask), batched, Ht, Wt, C, B, W, H,
+                                      boundary, cap, _ptr(pyramid) if pyramid.numel() else ctypes.c_void_p(0),
+                                      _ptr(out), _stream(dev))
+    _check(rc, "mr_texture_mip_forward")
+    return out, pyramid
+
+
+def texture_mip_pyramid(tex, max_mip_level=None):
+    """tex [Ht,Wt,C] or [Bt,Ht,Wt,C] f32 -> the pyramid levels 1 .. L-1 as a list of [Bt,Hl,Wl,C] tensors (Bt = 1
+    for a shared texture), built by the kernel texture_mip_forward uses."""
+    batched = torch.is_tensor(tex) and tex.dim() == 4
+    B = tex.shape[0] if batched else 1
+    uv = torch.zeros(B, 1, 1, 2, dtype=_F32, device=tex.device)
+    uv_da = torch.zeros(B, 1, 1, 4, dtype=_F32, device=tex.device)
+    _, pyramid = texture_mip_forward(tex, uv, uv_da, None, "wrap", max_mip_level)
+    return _mip_pyramid_views(pyramid, tex, texture_mip_levels(tex.shape[-3], tex.shape[-2], max_mip_level))
+
+
+def texture_mip_backward(dout, tex, pyramid, uv, uv_da, mask=None, boundary_mode="wrap", max_mip_level=None,
+                         want_tex=True, want_uv=True):
+    """-> (dtex with tex's shape, duv [B,H,W,2]); an unwanted gradient is None.  pyramid: texture_mip_forward's."""
+    B, H, W, Ht, Wt, C, batched, boundary, cap = _chk_texture_mip(tex, uv, uv_da, mask, boundary_mode, max_mip_level)
+    _chk("upstream gradient", dout, _F32, B, H, W, C)
+    L = lib()
+    _chk("pyramid", pyramid, _F32, L.mr_texture_mip_pyramid_bytes(batched, Ht, Wt, C, B, cap) // 4)
+    dev = _require_device(*[t for t in (dout, tex, pyramid, uv, uv_da, mask) if t is not None])
+    dout = _aligned16(dout.contiguous())
+    tex, uv, uv_da = _aligned16(tex.contiguous()), _aligned16(uv.contiguous()), _aligned16(uv_da.contiguous())
+    pyramid = _aligned16(pyramid.contiguous())
+    mask = mask.contiguous() if mask is not None else None
+    dtex = torch.empty(tex.shape, dtype=_F32, device=dev) if want_tex else None
+    duv = torch.empty(B, H, W, 2, dtype=_F32, device=dev) if want_uv else None
+    if B == 0 or not (want_tex or want_uv):
+        return (dtex.zero_() if dtex is not None else None), duv
+    with torch.cuda.device(dev):
+        _sync_deterministic()
+        ws, have = None, 0
+        if want_tex:
+            ws, have = _workspace(dev, L.mr_texture_mip_backward_workspace_bytes(batched, Ht, Wt, C, B, W, H, cap))
+        rc = L.mr_texture_mip_backward(_ptr(dout), _ptr(tex), _ptr(pyramid) if pyramid.numel() else ctypes.c_void_p(0),
+                                       _ptr(uv), _ptr(uv_da), _ptr(mask), batched, Ht, Wt, C, B, W, H, boundary, cap,
+                                       _ptr(dtex), _ptr(duv), _ptr(ws), have, _stream(dev))
+    _check(rc, "mr_texture_mip_backward")
+    return dtex, duv
+
+
+def attribute_derivatives(ids, bary, clip, triangles, attributes, attribute_triangles=None):
+    """ids [B,H,W] i32, bary [B,H,W,3], clip [B,V,4], triangles [T,3] i32, attributes [B,Va,A] f32 (1 <= A <= 4),
+    attribute_triangles [T,3] i32 or None (then Va = V) -> [B,H,W,A,2] f32: the screen-space derivatives
+    (d a / d X, d a / d Y) of the perspective-correct interpolation per pixel step, 0 on the background."""
+    B, V, T = _chk_mesh(clip, triangles)
+    H, W = _chk_gbuffer(ids, bary, B)
+    _chk("attributes", attributes, _F32, B, None, None)
+    Va, A = attributes.shape[1], attributes.shape[2]
+    if not 1 <= A <= 4:
+        raise ValueError("attribute_derivatives takes 1 to 4 attributes, got %d" % A)
+    if attribute_triangles is not None:
+        _chk("attribute_triangles", attribute_triangles, _I32, T, 3)
+    elif Va != V:
+        raise ValueError("attributes must have one row per vertex when attribute_triangles is None")
+    if T < 1 or V < 1 or Va < 1 or B > 65535 or H * W > 1 << 30:
+        raise ValueError("attribute_derivatives needs at least one triangle and vertex, at most 65535 images of at "
+                         "most 2^30 pixels")
+    dev = _require_device(*[t for t in (ids, bary, clip, triangles, attributes, attribute_triangles) if t is not None])
+    L = lib()
+    ids, bary, clip = ids.contiguous(), bary.contiguous(), _aligned16(clip.contiguous())
+    triangles, attributes = triangles.contiguous(), attributes.contiguous()
+    attribute_triangles = attribute_triangles.contiguous() if attribute_triangles is not None else None
+    out = torch.empty(B, H, W, A, 2, dtype=_F32, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.mr_attribute_derivatives(_ptr(ids), _ptr(bary), _ptr(clip), _ptr(triangles), _ptr(attributes),
+                                        _ptr(attribute_triangles), B, V, T, Va, W, H, A, _ptr(out), _stream(dev))
+    _check(rc, "mr_attribute_derivatives")
+    return out
 
 
 def shade_backward(drgba, ids, bary, clip, normals, positions, diffuse, triangles, light_positions,

@@ -782,6 +782,70 @@ int mr_texture_backward(const float *dout, const float *tex, const float *uv, co
                                      workspace, (hipStream_t)stream);
 }
 
+int mr_texture_mip_levels(int Ht, int Wt, int max_level) {
+  if (Ht < 1 || Wt < 1 || Ht > 65536 || Wt > 65536) return 0;
+  return mr::texture_mip_levels(Ht, Wt, max_level);
+}
+
+size_t mr_texture_mip_pyramid_bytes(int tex_batched, int Ht, int Wt, int C, int B, int max_level) {
+  if (bad_texture_dims(tex_batched, Ht, Wt, C, B, 1, 1)) return 0;
+  return mr::texture_mip_pyramid_floats(tex_batched, Ht, Wt, C, B, mr::texture_mip_levels(Ht, Wt, max_level)) *
+         sizeof(float);
+}
+
+int mr_texture_mip_forward(const float *tex, const float *uv, const float *uv_da, const float *mask, int tex_batched,
+                           int Ht, int Wt, int C, int B, int W, int H, int boundary, int max_level, float *pyramid,
+                           float *out, void *stream) {
+  if (bad_texture_dims(tex_batched, Ht, Wt, C, B, W, H) || bad_boundary(boundary)) return MR_EINVAL;
+  if (B == 0) return MR_OK;
+  const int L = mr::texture_mip_levels(Ht, Wt, max_level);
+  if (!tex || !uv || !uv_da || !out || misaligned(tex, 16) || misaligned(out, 16) || misaligned(uv, 8) ||
+      misaligned(uv_da, 16))
+    return MR_EINVAL;
+  if (L > 1 && (!pyramid || misaligned(pyramid, 16))) return MR_EINVAL;
+  return mr::launch_texture_mip_forward(tex, tex_batched, Ht, Wt, C, L, uv, uv_da, mask, B, W, H, boundary, pyramid,
+                                        out, (hipStream_t)stream);
+}
+
+size_t mr_texture_mip_backward_workspace_bytes(int tex_batched, int Ht, int Wt, int C, int B, int W, int H,
+                                               int max_level) {
+  if (bad_texture_dims(tex_batched, Ht, Wt, C, B, W, H)) return 0;
+  return mr::texture_mip_backward_ws(tex_batched, Ht, Wt, C, B, mr::texture_mip_levels(Ht, Wt, max_level));
+}
+
+int mr_texture_mip_backward(const float *dout, const float *tex, const float *pyramid, const float *uv,
+                            const float *uv_da, const float *mask, int tex_batched, int Ht, int Wt, int C, int B,
+                            int W, int H, int boundary, int max_level, float *dtex, float *duv, void *workspace,
+                            size_t workspace_bytes, void *stream) {
+  if (bad_texture_dims(tex_batched, Ht, Wt, C, B, W, H) || bad_boundary(boundary)) return MR_EINVAL;
+  if (B == 0) return MR_OK;
+  const int L = mr::texture_mip_levels(Ht, Wt, max_level);
+  if (!dout || !tex || !uv || !uv_da || misaligned(dout, 16) || misaligned(tex, 16) || misaligned(uv, 8) ||
+      misaligned(uv_da, 16))
+    return MR_EINVAL;
+  if (L > 1 && (!pyramid || misaligned(pyramid, 16))) return MR_EINVAL;
+  if ((dtex && misaligned(dtex, 16)) || (duv && misaligned(duv, 8))) return MR_EINVAL;
+  if (dtex) {
+    const int rc = check_ws(workspace, workspace_bytes, mr::texture_mip_backward_ws(tex_batched, Ht, Wt, C, B, L));
+    if (rc != MR_OK) return rc;
+  }
+  return mr::launch_texture_mip_backward(dout, tex, pyramid, tex_batched, Ht, Wt, C, L, uv, uv_da, mask, B, W, H,
+                                         boundary, dtex, duv, workspace, (hipStream_t)stream);
+}
+
+int mr_attribute_derivatives(const int32_t *ids, const float *bary, const float *clip, const int32_t *triangles,
+                             const float *attributes, const int32_t *attribute_triangles, int B, int V, int T,
+                             int Va, int W, int H, int A, float *out, void *stream) {
+  if (bad_dims(B, V, T, W, H) || A < 1 || A > 4 || T < 1 || V < 1 || Va < 1 || B > 65535 ||
+      (size_t)W * H > ((size_t)1 << 30))
+    return MR_EINVAL;
+  if (B == 0) return MR_OK;
+  if (!ids || !bary || !clip || !triangles || !attributes || !out || misaligned(clip, 16) || misaligned(out, 8))
+    return MR_EINVAL;
+  return mr::launch_attribute_derivatives(ids, bary, clip, triangles, attributes, attribute_triangles, B, V, T, Va, W,
+                                          H, A, out, (hipStream_t)stream);
+}
+
 int mr_tone_map(const float *image, int B, size_t elements_per_image, float gamma, int32_t *max_scratch,
                 float *out_f32, uint8_t *out_u8, void *stream) {
   if (B < 0) return MR_EINVAL;

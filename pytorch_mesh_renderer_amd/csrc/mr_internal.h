@@ -263,6 +263,19 @@ int launch_texture_forward(const float *tex, int tex_batched, int Ht, int Wt, in
 int launch_texture_backward(const float *dout, const float *tex, int tex_batched, int Ht, int Wt, int C,
                             const float *uv, const float *mask, int B, int W, int H, int boundary, float *dtex,
                             float *duv, void *ws, hipStream_t s);
+// mipmapped trilinear texture sampling and screen-space attribute derivatives (texture_mip.hip)
+int texture_mip_levels(int Ht, int Wt, int max_level);
+size_t texture_mip_pyramid_floats(int tex_batched, int Ht, int Wt, int C, int B, int L);
+size_t texture_mip_backward_ws(int tex_batched, int Ht, int Wt, int C, int B, int L);
+int launch_texture_mip_forward(const float *tex, int tex_batched, int Ht, int Wt, int C, int L, const float *uv,
+                               const float *uv_da, const float *mask, int B, int W, int H, int boundary, float *pyr,
+                               float *out, hipStream_t s);
+int launch_texture_mip_backward(const float *dout, const float *tex, const float *pyr, int tex_batched, int Ht, int Wt,
+                                int C, int L, const float *uv, const float *uv_da, const float *mask, int B, int W,
+                                int H, int boundary, float *dtex, float *duv, void *ws, hipStream_t s);
+int launch_attribute_derivatives(const int32_t *ids, const float *bary, const float *clip, const int32_t *tris,
+                                 const float *attrs, const int32_t *attr_tris, int B, int V, int T, int Va, int W,
+                                 int H, int A, float *out, hipStream_t s);
 int soft_max_lights();
 int launch_debug_soft_nearest(const float *p, const float *a, const float *b, int n, float *out, hipStream_t s);
 size_t soft_ws(int B, int V, int T, int W, int H);

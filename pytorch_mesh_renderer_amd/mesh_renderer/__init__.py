@@ -3,7 +3,8 @@ from .render import render, tone_mapper, tone_mapper_uint8, to_uint8
 from .rasterize import rasterize
 from .antialiasing import antialias, antialias_topology
 from .sh_lighting import render_sh, sh_shader
-from .texturing import render_textured, texture
+from .texturing import (attribute_derivatives, render_textured, render_textured_filtered, texture, texture_filtered,
+                        texture_mip_levels)
 from . import losses
 from . import regularizers
 from .graphs import capture_step, CapturedStep

@@ -7,7 +7,13 @@ and the fraction of the backward's 64 x 16 tiles whose footprint fits the LDS wi
   backward  read dout 12 + uv 8 + mask 4 B/px, write duv 8 B/px                       (32 B/px)
             (float atomics, and the deterministic mode: set_deterministic(True))
 
+--filter linear-mipmap-linear (or both, in one session) times the mipmapped trilinear sampler on the same job: uv_da
+from attribute_derivatives once, then mr_texture_mip_forward (pyramid build + sampling; it also writes uv_da's
+16 B/px) and mr_texture_mip_backward (scatter into the gradient pyramid + fold).  Per-kernel times of k_mip_build,
+k_tex_mip_forward, k_tex_mip_backward and k_mip_fold: run this tool under rocprofv3 --kernel-trace --stats.
+
     python tools/texture_bench.py [--batch 32] [--size 1024] [--textures 256,1024,4096] [--iters 20]
+                                  [--filter linear|linear-mipmap-linear|both]
 """
 import argparse
 import json
@@ -64,6 +70,7 @@ def main():
     parser.add_argument("--size", type=int, default=1024)
     parser.add_argument("--textures", default="256,1024,4096")
     parser.add_argument("--iters", type=int, default=20)
+    parser.add_argument("--filter", default="linear", choices=["linear", "linear-mipmap-linear", "both"])
     args = parser.parse_args()
     dev = torch.device("cuda:0")
     B, S = args.batch, args.size
@@ -76,31 +83,51 @@ def main():
         ids, bary, _ = _native.rasterize_forward(clip.contiguous(), tris, S, S)
         attrs = torch.cat([uvs, torch.ones(uvs.shape[0], 1, device=dev)], 1).unsqueeze(0).expand(B, -1, -1)
         px = _native.interpolate_forward(ids, bary, attrs.contiguous(), uv_tris, torch.zeros(3, device=dev))
+        uv_da = None
+        if args.filter != "linear":
+            uv_da = _native.attribute_derivatives(ids, bary, clip.contiguous(), tris,
+                                                  uvs.unsqueeze(0).expand(B, -1, -1).contiguous(), uv_tris).view(B, S, S, 4)
     uv, mask = px[..., 0:2].contiguous(), px[..., 2].contiguous()
     del ids, bary, px
     dout = torch.randn(B, S, S, 3, device=dev)
     pixels = B * S * S
     results = []
+    filters = ["linear", "linear-mipmap-linear"] if args.filter == "both" else [args.filter]
     for St in [int(t) for t in args.textures.split(",")]:
         tex = torch.rand(St, St, 3, device=dev)
-        fwd_us = timed(lambda: _native.texture_forward(tex, uv, mask, "wrap"), args.iters)
-        bwd_us = timed(lambda: _native.texture_backward(dout, tex, uv, mask, "wrap"), args.iters)
-        before = _native.set_deterministic(True)
-        try:
-            det_us = timed(lambda: _native.texture_backward(dout, tex, uv, mask, "wrap"), args.iters)
-        finally:
-            _native.set_deterministic(before)
-        used, fit_float, fit_fixed = tile_paths(uv, mask, St)
-        results.append({
-            "shape": [B, S, S], "texture": [St, St, 3], "covered_fraction": round(float((mask > 0.5).float().mean()), 3),
-            "tiles_sampling": used, "tiles_in_float_window": round(fit_float / max(used, 1), 3),
-            "tiles_in_fixed_window": round(fit_fixed / max(used, 1), 3),
-            "forward_us": round(fwd_us, 1), "backward_us": round(bwd_us, 1), "backward_deterministic_us": round(det_us, 1),
-            "forward_fraction_of_8TBs": round(24 * pixels / (fwd_us * 1e-6) / PEAK, 3),
-            "backward_fraction_of_8TBs": round(32 * pixels / (bwd_us * 1e-6) / PEAK, 3),
-            "backward_deterministic_fraction_of_8TBs": round(32 * pixels / (det_us * 1e-6) / PEAK, 3),
-        })
-        print(json.dumps(results[-1]), flush=True)
+        for mode in filters:
+            if mode == "linear":
+                forward = lambda: _native.texture_forward(tex, uv, mask, "wrap")
+                backward = lambda: _native.texture_backward(dout, tex, uv, mask, "wrap")
+            else:
+                pyramid = _native.texture_mip_forward(tex, uv, uv_da, mask, "wrap")[1]
+                forward = lambda: _native.texture_mip_forward(tex, uv, uv_da, mask, "wrap")
+                backward = lambda: _native.texture_mip_backward(dout, tex, pyramid, uv, uv_da, mask, "wrap")
+            fwd_us = timed(forward, args.iters)
+            bwd_us = timed(backward, args.iters)
+            before = _native.set_deterministic(True)
+            try:
+                det_us = timed(backward, args.iters)
+            finally:
+                _native.set_deterministic(before)
+            row = {"filter": mode, "shape": [B, S, S], "texture": [St, St, 3],
+                   "covered_fraction": round(float((mask > 0.5).float().mean()), 3),
+                   "forward_us": round(fwd_us, 1), "backward_us": round(bwd_us, 1),
+                   "backward_deterministic_us": round(det_us, 1)}
+            if mode == "linear":
+                used, fit_float, fit_fixed = tile_paths(uv, mask, St)
+                row.update({
+                    "tiles_sampling": used, "tiles_in_float_window": round(fit_float / max(used, 1), 3),
+                    "tiles_in_fixed_window": round(fit_fixed / max(used, 1), 3),
+                    "forward_fraction_of_8TBs": round(24 * pixels / (fwd_us * 1e-6) / PEAK, 3),
+                    "backward_fraction_of_8TBs": round(32 * pixels / (bwd_us * 1e-6) / PEAK, 3),
+                    "backward_deterministic_fraction_of_8TBs": round(32 * pixels / (det_us * 1e-6) / PEAK, 3)})
+            else:
+                lod = 0.5 * torch.log2(torch.maximum((uv_da[..., 0] * St) ** 2 + (uv_da[..., 2] * St) ** 2,
+                                                     (uv_da[..., 1] * St) ** 2 + (uv_da[..., 3] * St) ** 2))
+                lod = lod[mask > 0.5].clamp(0, _native.texture_mip_levels(St, St) - 1)
+                row.update({"levels": _native.texture_mip_levels(St, St), "median_lod": round(float(lod.median()), 2)})
+            print(json.dumps(row), flush=True)
         del tex
 
 
