@@ -36,6 +36,7 @@
 #pragma once
 
 #include <type_traits>
+#include <utility>
 
 #include "det_fixed.h"
 #include "mr_internal.h"
@@ -737,6 +738,21 @@ static __global__ __launch_bounds__(kSumRowThreads) void k_sum_strip_rows(const 
     for (int k = 0; k < kParts; ++k) t += s_part[k][slot];
     out[(size_t)img * row + slot] = t;
   }
+}
+
+// A run-time value as a compile-time one: static_switch(v, std::integer_sequence<int, 1, 2>{}, f) calls
+// f(std::integral_constant<int, V>{}) for the listed V that equals v (a value not in the list: MR_EINVAL),
+// static_switch(flag, f) calls f(std::true_type{}) or f(std::false_type{}); f is a generic lambda that returns
+// an MR_* code and reads the constant as decltype(arg)::value.  How the launchers pick a functor's template arguments.
+template <int... Vs, class F>
+inline int static_switch(int v, std::integer_sequence<int, Vs...>, F &&f) {
+  int rc = MR_EINVAL;
+  (void)((v == Vs && ((rc = f(std::integral_constant<int, Vs>{})), true)) || ...);
+  return rc;
+}
+template <class F>
+inline int static_switch(bool v, F &&f) {
+  return v ? f(std::true_type{}) : f(std::false_type{});
 }
 
 // strips (= workgroups = `region`s) of k_accumulate_rows<Fn> per image

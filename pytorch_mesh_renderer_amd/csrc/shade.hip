@@ -417,6 +417,7 @@ struct ShadeGradFn {
 // position attribute's gradient before the outer product with the barycentrics: 9 sums per triangle fewer to
 // keep in registers, to restart, to park, to merge and to commit (18 -> 9 for vertex gradients alone), for nine
 // multiply-adds with scalar operands; the gather then finds zeros in the clip columns.
+// (Nothing instantiates FOLD = true any more: every folding call runs ShadeFoldLaneFn or ShadeDiffLaneFn below.)
 template <int L, bool SIGNS, bool LG, int GROUPS, bool OPAQUE = false, bool FOLD = false>
 struct ShadeLaneFn : ShadeGradFn<L, SIGNS, LG> {
   using Base = ShadeGradFn<L, SIGNS, LG>;
@@ -830,17 +831,183 @@ int launch_shade_forward(const int32_t *ids, const float *bary, const float *nor
 
 size_t shade_backward_prepared_bytes(int B, int T) { return fold_prepared_bytes(B, T); }
 
-size_t shade_backward_ws(int B, int V, int T, int W, int H) {
-  return shade_acc_bytes(B, T) + align_up((size_t)B * T * sizeof(BwdRec), 256) + corner_bytes(B, T) +
-         kDetBlockBytes + light_rows_bytes(B, W, H) + align_up((size_t)B * T * sizeof(FoldRec), 256) +
-         align_up((size_t)B * V * 4 * sizeof(float), 256);  // last two: the folded kernel's records, dclip scratch
-}
-
 thread_local int g_deterministic = 0;  // mr_set_deterministic
 // mr_debug_set_shade_backward_kernel: 0 = automatic (lane-accumulating kernel where it exists: no
 // light gradients, not every attribute gradient wanted, not deterministic), 1 = always the rows
 // kernel, 2 = the lane-accumulating kernel wherever it is instantiated
 thread_local int g_shade_backward_kernel = 0;
+
+namespace {
+
+// The backward's workspace: the byte offset of every sub-buffer, in this order, and their sum.
+struct ShadeBackwardLayout {
+  size_t acc, recs, corners, det_block, light_rows, fold_recs, dclip, total;
+};
+ShadeBackwardLayout shade_backward_layout(int B, int V, int T, int W, int H) {
+  ShadeBackwardLayout l{};
+  const auto take = [&l](size_t bytes) { const size_t offset = l.total; l.total += bytes; return offset; };
+  l.acc = take(shade_acc_bytes(B, T));
+  l.recs = take(align_up((size_t)B * T * sizeof(BwdRec), 256));
+  l.corners = take(corner_bytes(B, T));
+  l.det_block = take(kDetBlockBytes);
+  l.light_rows = take(light_rows_bytes(B, W, H));
+  l.fold_recs = take(align_up((size_t)B * T * sizeof(FoldRec), 256));   // the difference-basis kernels' records
+  l.dclip = take(align_up((size_t)B * V * 4 * sizeof(float), 256));     // the clip-space gradient nobody asked for
+  return l;
+}
+
+// What the choice of kernels depends on, and nothing else (mr_shade_backward / _l1 have validated the call).
+struct ShadeBackwardCase {
+  int L;
+  bool signs;                                    // the upstream gradient is the L1 loss's sign codes
+  bool light_grads, normals, diffuse, clip;      // gradients wanted (positions: always)
+  bool transforms, adjacency, records, prepared; // optional inputs given
+  bool normalised;                               // MR_GBUFFER_NORMALISED
+  bool deterministic;
+  int kernel;                                    // mr_debug_set_shade_backward_kernel
+  bool nonempty;                                 // T > 0 && V > 0
+};
+enum class ShadePixelPass { kNone, kRows, kLanes, kFoldLanes, kDiffLanes };   // ShadeGradFn, ShadeLaneFn, ShadeFoldLaneFn, ShadeDiffLaneFn
+enum class ShadeVertexPass { kNone, kGatherFold, kGather, kScatter };
+struct ShadeBackwardPlan {
+  int rc = MR_OK;                  // MR_EINVAL: a rejected case, nothing is launched
+  ShadePixelPass pixel = ShadePixelPass::kNone;
+  int NL = 0, groups = 7;          // the functor's template arguments: lights in registers (0: run-time loop), attribute groups,
+  bool opaque = false, folded = false, LG = false;   // OPAQUE (ShadeLaneFn), FOLD (ShadeDiffLaneFn), light gradients
+  bool fused_clear = false;        // k_bwd_setup clears the accumulator rows and light_grads, the gather writes every output once
+  bool use_prepared = false;       // records and cleared rows come from mr_render_forward's block: no setup launch
+  bool dclip_scratch = false;      // the clip-space sums are formed, but land in the workspace
+  ShadeVertexPass vertex = ShadeVertexPass::kNone;
+};
+
+// The decision table of DESIGN.md 4.4.  Every compile-time A/B switch (MR_SHADE_*) is one term here.
+ShadeBackwardPlan plan_shade_backward(const ShadeBackwardCase &c) {
+  ShadeBackwardPlan p;
+  p.dclip_scratch = !c.clip;
+  if (!c.nonempty) return p;   // the outputs are cleared, nothing else runs
+  const auto rejected = [&p] { p.rc = MR_EINVAL; return p; };
+  if (c.deterministic && !c.adjacency) return rejected();   // the scatter path is float atomics only
+  if (c.light_grads && c.L > kMaxLights) return rejected(); // light gradients: four lights per call (see ShadeGradFn)
+  p.NL = c.L <= kMaxLights ? c.L : 0;
+  p.groups = (c.normals ? 1 : 0) | 2 | (c.diffuse ? 4 : 0);
+  p.LG = c.light_grads;
+  // The lane kernels: float atomics; no variant for positions + diffuse (6); with light gradients one or two
+  // lights (6 L + 3 more per-lane sums; three and four stay on the rows kernel).
+  const bool lanes = !c.deterministic && p.groups != 6 && c.kernel != 1 && (!c.light_grads || (MR_SHADE_LANES_LG && c.L <= 2));
+  // Their difference-basis forms (ShadeFoldLaneFn, ShadeDiffLaneFn) leave the alpha terms out and read FoldRecs,
+  // which the setup kernel derives from the forward's corner records (or the forward wrote into `prepared`).
+  const bool diff_basis = lanes && MR_SHADE_FOLD_DIFF && c.normalised;
+  // No clip-space gradient wanted on its own: the pull-back through the transforms is folded into the pixel pass
+  // and no clip-space sums exist at all.
+  const bool fold = diff_basis && MR_SHADE_LANES_FOLD && !c.clip && c.transforms &&
+                    (c.light_grads ? c.records : (p.groups == 2 || c.records || c.prepared));
+  const bool fold_diff = fold && !c.light_grads && p.groups == 2 && (c.records || c.prepared);   // vertex gradients only
+  const bool diff = !fold_diff && diff_basis && c.records && c.adjacency;
+  // Folding was chosen, but only the difference-basis kernels fold and this caller's records do not reach them:
+  //   * transforms, no clip gradient, vertex gradients only, neither corner_records nor prepared;
+  //   * prepared without corner_records, normals or diffuse gradients wanted.
+  if (fold && !diff && !fold_diff) return rejected();
+  p.folded = fold;
+  p.dclip_scratch = !c.clip && !fold;
+  p.fused_clear = c.adjacency && !c.deterministic;   // (always the case with `fold`: transforms imply the adjacency)
+  p.use_prepared = fold_diff && c.prepared && MR_SHADE_USE_PREPARED;
+  p.opaque = c.normalised && !c.light_grads;
+  p.pixel = diff ? ShadePixelPass::kDiffLanes : fold_diff ? ShadePixelPass::kFoldLanes
+          : lanes ? ShadePixelPass::kLanes : ShadePixelPass::kRows;
+  p.vertex = fold_diff ? ShadeVertexPass::kGatherFold : c.adjacency ? ShadeVertexPass::kGather : ShadeVertexPass::kScatter;
+  return p;
+}
+
+// What the pixel pass's functors are built from, whichever family runs.
+struct ShadePixelArgs {
+  const float *drgba;   // a dense upstream image, or the L1 loss's sign codes, its upstream scalar and 1 / element count
+  const uint8_t *signs;
+  const float *sign_upstream;
+  float sign_inv_n;
+  const int32_t *ids;
+  const float *bary;
+  const CornerRec *corners;
+  const BwdRec *recs;
+  Lights lights;
+  float *light_rows;
+  int B, T, W, H;
+  const float *transforms;   // these three: the difference-basis functors only
+  const uint8_t *empty_regions;
+  const FoldRec *fold_recs;
+  float *acc;
+  const DetBlock *det;       // the deterministic mode's block (rows kernel only), or nullptr
+};
+template <int NL, bool SIGNS, bool LG>
+ShadeGradFn<NL, SIGNS, LG> shade_grad_fn(const ShadePixelArgs &a, bool diff_basis) {
+  return {(const float4 *)a.drgba, a.signs, a.sign_upstream, SIGNS ? a.sign_inv_n : 0.0f, a.ids, (const F3 *)a.bary,
+          a.corners, a.recs, a.lights, LG ? a.light_rows : nullptr, a.T, a.W, a.H,
+          diff_basis ? a.transforms : nullptr, diff_basis ? a.empty_regions : nullptr};
+}
+template <class Fn>
+int launch_shade_lanes(const Fn &fn, const ShadePixelArgs &a, hipStream_t s) {
+  return launch_accumulate_lanes(fn, a.B, a.T, a.W, a.H, a.acc, s);
+}
+
+// The plan's pixel pass for one (NL, SIGNS, LG): the family and the rest of its template arguments.  Light
+// gradients exist for lights kept in registers only -- one to four in the rows kernel, one or two in the lane kernels.
+template <int NL, bool SIGNS, bool LG>
+int launch_shade_pixels_of(const ShadeBackwardPlan &plan, const ShadePixelArgs &a, hipStream_t s) {
+  constexpr std::integer_sequence<int, 2, 3, 7> kGroupSets{};
+  constexpr bool kLaneLG = NL == 1 || NL == 2;
+  switch (plan.pixel) {
+    case ShadePixelPass::kRows:
+      if constexpr (!LG || NL > 0)
+        return launch_accumulate_rows(shade_grad_fn<NL, SIGNS, LG>(a, false), a.B, a.T, a.W, a.H, a.acc, s, a.det);
+      break;
+    case ShadePixelPass::kFoldLanes:
+      if constexpr (!LG) {
+        const ShadeFoldLaneFn<NL, SIGNS> fn{shade_grad_fn<NL, SIGNS, false>(a, true), a.fold_recs};
+        return launch_shade_lanes(fn, a, s);
+      }
+      break;
+    case ShadePixelPass::kLanes:
+      if constexpr (!LG || kLaneLG)
+        return static_switch(plan.groups, kGroupSets, [&](auto groups) {
+          if constexpr (LG) {
+            const ShadeLaneFn<NL, SIGNS, true, decltype(groups)::value, false> fn{shade_grad_fn<NL, SIGNS, true>(a, false)};
+            return launch_shade_lanes(fn, a, s);
+          } else {
+            return static_switch(plan.opaque, [&](auto opaque) {
+              const ShadeLaneFn<NL, SIGNS, false, decltype(groups)::value, decltype(opaque)::value> fn{
+                  shade_grad_fn<NL, SIGNS, false>(a, false)};
+              return launch_shade_lanes(fn, a, s);
+            });
+          }
+        });
+      break;
+    case ShadePixelPass::kDiffLanes:
+      if constexpr (!LG || kLaneLG)
+        return static_switch(plan.groups, kGroupSets, [&](auto groups) {
+          return static_switch(plan.folded, [&](auto folded) {
+            const ShadeDiffLaneFn<NL, SIGNS, decltype(groups)::value, decltype(folded)::value, LG> fn{
+                shade_grad_fn<NL, SIGNS, LG>(a, true), a.fold_recs};
+            return launch_shade_lanes(fn, a, s);
+          });
+        });
+      break;
+    case ShadePixelPass::kNone:
+      break;
+  }
+  return MR_EINVAL;
+}
+int launch_shade_pixels(const ShadeBackwardPlan &plan, const ShadePixelArgs &a, hipStream_t s) {
+  return static_switch(plan.NL, std::make_integer_sequence<int, kMaxLights + 1>{}, [&](auto nl) {
+    return static_switch(a.signs != nullptr, [&](auto signs) {
+      return static_switch(plan.LG, [&](auto lg) {
+        return launch_shade_pixels_of<decltype(nl)::value, decltype(signs)::value, decltype(lg)::value>(plan, a, s);
+      });
+    });
+  });
+}
+
+}  // namespace
+
+size_t shade_backward_ws(int B, int V, int T, int W, int H) { return shade_backward_layout(B, V, T, W, H).total; }
 
 int launch_shade_backward(const float *drgba, const uint8_t *signs, const float *sign_upstream,
                           const int32_t *ids, const float *bary,
@@ -853,33 +1020,26 @@ int launch_shade_backward(const float *drgba, const uint8_t *signs, const float 
                           const float *transforms, int gbuffer_flags, void *prepared, const uint8_t *empty_regions, void *ws,
                           hipStream_t s) {
   if (B == 0) return MR_OK;
-  if (transforms && !(vertex_offsets && vertex_entries)) return MR_EINVAL;  // the gather applies them
-  if (!dclip && !transforms) return MR_EINVAL;  // without the pull-back the clip-space gradient IS the vertex gradient
+  const bool det = g_deterministic != 0;
+  const ShadeBackwardPlan plan = plan_shade_backward(
+      {L, signs != nullptr, light_grads != nullptr, dnormals != nullptr, ddiffuse != nullptr, dclip != nullptr,
+       transforms != nullptr, vertex_offsets && vertex_entries, corner_records != nullptr, prepared != nullptr,
+       (gbuffer_flags & MR_GBUFFER_NORMALISED) != 0, det, g_shade_backward_kernel, T > 0 && V > 0});
+  if (plan.rc != MR_OK) return plan.rc;
+  const ShadeBackwardLayout at = shade_backward_layout(B, V, T, W, H);
+  char *const base = (char *)ws;
+  if (plan.dclip_scratch) dclip = (float *)(base + at.dclip);
   const size_t v3 = (size_t)B * V * 3 * sizeof(float), v4 = (size_t)B * V * 4 * sizeof(float);
   const size_t lg = light_grads ? (size_t)B * (L * 6 + 3) * sizeof(float) : 0;  // nullptr: not wanted
-  const bool det = g_deterministic != 0;
-  // dclip == nullptr (with transforms): the caller wants the gradient of the world-space positions only.  Where
-  // the lane kernel has the variant, the pull-back through the transforms is folded into the pixel pass
-  // (ShadeLaneFn<..., FOLD>) and no clip-space sums exist at all; elsewhere the clip gradient goes to scratch.
-  const int groups_wanted = (dnormals ? 1 : 0) | 2 | (ddiffuse ? 4 : 0);   // (6 -- positions + diffuse -- has no lane kernel)
-  const bool lg_lanes = light_grads && MR_SHADE_LANES_LG && L >= 1 && L <= 2 && corner_records != nullptr;   // ShadeDiffLaneFn<..., LG>
-  const bool fold_any = !dclip && transforms && MR_SHADE_LANES_FOLD && (!light_grads || lg_lanes) && !det && groups_wanted != 6 &&
-                        (gbuffer_flags & MR_GBUFFER_NORMALISED) != 0 && g_shade_backward_kernel != 1 && T > 0 && V > 0 &&
-                        (corner_records != nullptr || prepared != nullptr) && MR_SHADE_FOLD_DIFF;   // (any attribute groups)
-  const bool fold = fold_any || (!dclip && transforms && MR_SHADE_LANES_FOLD && !light_grads && !det && !dnormals && !ddiffuse &&
-                    (gbuffer_flags & MR_GBUFFER_NORMALISED) != 0 && g_shade_backward_kernel != 1 && T > 0 && V > 0);
-  if (!dclip && !fold)
-    dclip = (float *)((char *)ws + shade_backward_ws(B, V, T, W, H) - align_up((size_t)B * V * 4 * sizeof(float), 256));
   const float sign_inv_n = 1.0f / (float)((size_t)B * H * W * 4);  // the L1 mean runs over the whole image
   // With the vertex adjacency the gather writes every vertex output exactly once, and k_bwd_setup
   // clears the accumulator rows and light_grads on the side: no memset launches at all (two of
   // ~6 us each before).  (Not in the deterministic mode: its fixed-point side buffers are cleared
   // the plain way.)
-  const bool fused_clear = vertex_offsets && vertex_entries && !det && T > 0 && V > 0;
   // Otherwise the outputs are zeroed here.  A caller that lays them out back to back (dclip,
   // dnormals, dpositions, ddiffuse, light_grads -- _native.py does) gets ONE memset instead of five
   // launch-bound ones.
-  if (fused_clear) {   // (always the case with `fold`: transforms imply the adjacency, and it excludes det)
+  if (plan.fused_clear) {
   } else if (dnormals && ddiffuse && (char *)dnormals == (char *)dclip + v4 && (char *)dpositions == (char *)dnormals + v3 &&
              (char *)ddiffuse == (char *)dpositions + v3 && (char *)light_grads == (char *)ddiffuse + v3) {
     if (zero_async(dclip, v4 + 3 * v3 + lg, s) != hipSuccess) return check_launch();
@@ -892,32 +1052,21 @@ int launch_shade_backward(const float *drgba, const uint8_t *signs, const float 
     }
     if (light_grads && zero_async(light_grads, lg, s) != hipSuccess) return check_launch();
   }
-  if (T == 0 || V == 0) return MR_OK;
-  float *acc = (float *)ws;
-  BwdRec *recs = (BwdRec *)((char *)ws + shade_acc_bytes(B, T));
-  CornerRec *corners = (CornerRec *)((char *)recs + align_up((size_t)B * T * sizeof(BwdRec), 256));
-  DetBlock *det_block = (DetBlock *)((char *)corners + corner_bytes(B, T));
-  float *light_rows = (float *)((char *)det_block + kDetBlockBytes);
-  FoldRec *fold_recs = (FoldRec *)((char *)light_rows + light_rows_bytes(B, W, H));
-  const bool fold_diff = fold && MR_SHADE_FOLD_DIFF && (corner_records != nullptr || prepared != nullptr) && !dnormals && !ddiffuse &&
-                         !light_grads;   // (with light gradients: ShadeDiffLaneFn<..., LG>, below)
-  // the difference-basis pixel pass for every other lane-kernel case on a normalised G-buffer: normals / diffuse
-  // wanted, and / or the clip-space gradient wanted on its own, and (round 5, one or two lights) the light gradients
-  const bool diff_general = !fold_diff && MR_SHADE_FOLD_DIFF && corner_records != nullptr &&
-                            (!light_grads || (MR_SHADE_LANES_LG && L >= 1 && L <= 2)) && !det &&
-                            (gbuffer_flags & MR_GBUFFER_NORMALISED) != 0 && g_shade_backward_kernel != 1 &&
-                            vertex_offsets && vertex_entries && T > 0 && V > 0 && groups_wanted != 6;
+  if (plan.pixel == ShadePixelPass::kNone) return MR_OK;   // T == 0 || V == 0
+  float *acc = (float *)(base + at.acc);
+  BwdRec *recs = (BwdRec *)(base + at.recs);
+  CornerRec *corners = (CornerRec *)(base + at.corners);
+  DetBlock *det_block = (DetBlock *)(base + at.det_block);
+  float *light_rows = (float *)(base + at.light_rows);
+  FoldRec *fold_recs = (FoldRec *)(base + at.fold_recs);
   // `prepared` (mr_render_forward's backward_prepared: FoldRec[B*T] + cleared compact accumulator rows): the folded
   // kernel's setup launch is skipped, and the gather leaves the rows cleared again for the next backward call
-  const bool use_prepared = fold_diff && prepared != nullptr && MR_SHADE_USE_PREPARED;
-  if (fold && !fold_diff && !diff_general && !dclip) return MR_EINVAL;   // (cannot happen: every folding path is one of the two)
-  if (use_prepared) {
+  if (plan.use_prepared) {
     fold_recs = (FoldRec *)prepared;
     acc = (float *)((char *)prepared + fold_prepared_recs_bytes(B, T));
   }
-  if (det && !(vertex_offsets && vertex_entries)) return MR_EINVAL;  // the scatter path is atomics only
   const size_t acc_bytes = (size_t)B * T * 36 * (det ? sizeof(long long) : sizeof(float));
-  if (!fused_clear && zero_async(acc, acc_bytes, s) != hipSuccess) return check_launch();
+  if (!plan.fused_clear && zero_async(acc, acc_bytes, s) != hipSuccess) return check_launch();
   int rc = MR_OK;
   if (det) {
     // sign codes: every upstream gradient is +-sign_upstream[0] / n; a dense image: its largest |R|, |G| or |B|
@@ -925,209 +1074,60 @@ int launch_shade_backward(const float *drgba, const uint8_t *signs, const float 
                : launch_det_scale(drgba, (size_t)B * H * W * 4, 1.0f, det_block, s, /*rgb_of_rgba=*/true);
     if (rc != MR_OK) return rc;
   }
-  if (use_prepared) rc = MR_OK;
-  else
-  rc = fused_clear ? launch_bwd_setup(clip, tris, B, V, T, recs, s, acc, (fold_diff ? kFoldAccStride : 36) * sizeof(float), light_grads,
-                                      light_grads ? B * (L * 6 + 3) : 0, (fold_diff || diff_general) ? corner_records : nullptr,
-                                      (fold_diff || diff_general) ? fold_recs : nullptr,
-                                      fold ? transforms : nullptr)   // the folded kernels read the pulled form
-                   : launch_bwd_setup(clip, tris, B, V, T, recs, s);
-  if (rc != MR_OK) return rc;
+  const bool fold_lanes = plan.pixel == ShadePixelPass::kFoldLanes;   // compact accumulator rows
+  const bool diff_basis = fold_lanes || plan.pixel == ShadePixelPass::kDiffLanes;
+  if (!plan.use_prepared) {
+    rc = plan.fused_clear
+             ? launch_bwd_setup(clip, tris, B, V, T, recs, s, acc, (fold_lanes ? kFoldAccStride : 36) * sizeof(float), light_grads,
+                                light_grads ? B * (L * 6 + 3) : 0, diff_basis ? corner_records : nullptr,
+                                diff_basis ? fold_recs : nullptr,
+                                plan.folded ? transforms : nullptr)   // the folded kernels read the pulled form
+             : launch_bwd_setup(clip, tris, B, V, T, recs, s);
+    if (rc != MR_OK) return rc;
+  }
   if (corner_records) {  // the forward's records (same inputs): skip the gather
     corners = (CornerRec *)corner_records;
   } else {
     rc = launch_corner_setup(normals, positions, diffuse, tris, B, V, T, corners, s);
     if (rc != MR_OK) return rc;
   }
-  Lights lights{light_pos, light_col, ambient, L};
-  if (L > kMaxLights && light_grads) return MR_EINVAL;  // light gradients: four lights per call (see ShadeGradFn)
-  // Attribute gradients the caller wants (nullptr: not wanted).  The scatter path (no adjacency)
-  // writes all of them.
-  if ((!dnormals || !ddiffuse) && !(vertex_offsets && vertex_entries)) return MR_EINVAL;
-  const int groups = (dnormals ? 1 : 0) | 2 | (ddiffuse ? 4 : 0);
-  // with light gradients: one or two lights (6 L + 3 more per-lane sums; three and four stay on the rows kernel)
-  const bool lanes_exist = (!light_grads || (MR_SHADE_LANES_LG && L <= 2)) && !det && groups != 6 &&
-                           (groups != 7 || 1);
-  const bool use_lanes = lanes_exist && g_shade_backward_kernel != 1;
-  const bool opaque = (gbuffer_flags & MR_GBUFFER_NORMALISED) != 0;  // (the lane kernels only)
-#define MR_SHADE_LANES_O(NL, G, OPQ)                                                            \
-  {                                                                                             \
-    KernelTimer timer(MR_TIMER_SHADE_BACKWARD, s);                                              \
-    if (signs) {                                                                                \
-      ShadeLaneFn<NL, true, false, G, OPQ> fn{{nullptr, signs, sign_upstream, sign_inv_n, ids, (const F3 *)bary, \
-                                               corners, recs, lights, nullptr, T, W, H}};       \
-      rc = launch_accumulate_lanes(fn, B, T, W, H, acc, s);                                     \
-    } else {                                                                                    \
-      ShadeLaneFn<NL, false, false, G, OPQ> fn{{(const float4 *)drgba, nullptr, nullptr, 0.0f, ids, (const F3 *)bary, \
-                                                corners, recs, lights, nullptr, T, W, H}};      \
-      rc = launch_accumulate_lanes(fn, B, T, W, H, acc, s);                                     \
-    }                                                                                           \
+  {
+    KernelTimer timer(MR_TIMER_SHADE_BACKWARD, s);
+    rc = launch_shade_pixels(plan, {drgba, signs, sign_upstream, sign_inv_n, ids, bary, corners, recs,
+                                    Lights{light_pos, light_col, ambient, L}, light_rows, B, T, W, H, transforms,
+                                    empty_regions, fold_recs, acc, det ? det_block : nullptr}, s);
   }
-#define MR_SHADE_LANES_LGV(NL, G)                                                               \
-  {                                                                                             \
-    KernelTimer timer(MR_TIMER_SHADE_BACKWARD, s);                                              \
-    if (signs) {                                                                                \
-      ShadeLaneFn<NL, true, true, G, false> fn{{nullptr, signs, sign_upstream, sign_inv_n, ids, (const F3 *)bary, \
-                                                corners, recs, lights, light_rows, T, W, H}};   \
-      rc = launch_accumulate_lanes(fn, B, T, W, H, acc, s);                                     \
-    } else {                                                                                    \
-      ShadeLaneFn<NL, false, true, G, false> fn{{(const float4 *)drgba, nullptr, nullptr, 0.0f, ids, (const F3 *)bary, \
-                                                 corners, recs, lights, light_rows, T, W, H}};  \
-      rc = launch_accumulate_lanes(fn, B, T, W, H, acc, s);                                     \
-    }                                                                                           \
-  }
-#define MR_SHADE_LANES_FOLDED(NL)                                                               \
-  if (fold_diff) {                                                                              \
-    KernelTimer timer(MR_TIMER_SHADE_BACKWARD, s);                                              \
-    if (signs) {                                                                                \
-      ShadeFoldLaneFn<NL, true> fn{{nullptr, signs, sign_upstream, sign_inv_n, ids, (const F3 *)bary, corners, recs, \
-                                    lights, nullptr, T, W, H, transforms, empty_regions}, fold_recs};          \
-      rc = launch_accumulate_lanes(fn, B, T, W, H, acc, s);                                     \
-    } else {                                                                                    \
-      ShadeFoldLaneFn<NL, false> fn{{(const float4 *)drgba, nullptr, nullptr, 0.0f, ids, (const F3 *)bary, corners,  \
-                                     recs, lights, nullptr, T, W, H, transforms, empty_regions}, fold_recs};   \
-      rc = launch_accumulate_lanes(fn, B, T, W, H, acc, s);                                     \
-    }                                                                                           \
-  } else {                                                                                      \
-    KernelTimer timer(MR_TIMER_SHADE_BACKWARD, s);                                              \
-    if (signs) {                                                                                \
-      ShadeLaneFn<NL, true, false, 2, true, true> fn{{nullptr, signs, sign_upstream, sign_inv_n, ids, (const F3 *)bary, \
-                                                      corners, recs, lights, nullptr, T, W, H, transforms}};            \
-      rc = launch_accumulate_lanes(fn, B, T, W, H, acc, s);                                     \
-    } else {                                                                                    \
-      ShadeLaneFn<NL, false, false, 2, true, true> fn{{(const float4 *)drgba, nullptr, nullptr, 0.0f, ids, (const F3 *)bary, \
-                                                       corners, recs, lights, nullptr, T, W, H, transforms}};                \
-      rc = launch_accumulate_lanes(fn, B, T, W, H, acc, s);                                     \
-    }                                                                                           \
-  }
-#define MR_SHADE_LANES(NL, G)                                                                   \
-  if (fold) MR_SHADE_LANES_FOLDED(NL) else if (opaque) MR_SHADE_LANES_O(NL, G, true) else MR_SHADE_LANES_O(NL, G, false)
-#define MR_SHADE_LANES_LIGHTS(NL, G)   /* one or two lights: the variant with light gradients exists */ \
-  if (light_grads) MR_SHADE_LANES_LGV(NL, G) else MR_SHADE_LANES(NL, G)
-#define MR_SHADE_LANES_G(NL)                                                                    \
-  if (groups == 2) MR_SHADE_LANES(NL, 2) else if (groups == 3) MR_SHADE_LANES(NL, 3) else MR_SHADE_LANES(NL, 7)
-#define MR_SHADE_LANES_GL(NL)                                                                   \
-  if (groups == 2) MR_SHADE_LANES_LIGHTS(NL, 2) else if (groups == 3) MR_SHADE_LANES_LIGHTS(NL, 3) else MR_SHADE_LANES_LIGHTS(NL, 7)
-  if (diff_general && use_lanes) {
-    const bool folded = dclip == nullptr;   // (implies transforms)
-#define MR_SHADE_DIFF_LG(NL, G, F, LGV)                                                         \
-  {                                                                                             \
-    KernelTimer timer(MR_TIMER_SHADE_BACKWARD, s);                                              \
-    if (signs) {                                                                                \
-      ShadeDiffLaneFn<NL, true, G, F, LGV> fn{{nullptr, signs, sign_upstream, sign_inv_n, ids, (const F3 *)bary, corners, recs, \
-                                               lights, LGV ? light_rows : nullptr, T, W, H, transforms, empty_regions}, fold_recs};    \
-      rc = launch_accumulate_lanes(fn, B, T, W, H, acc, s);                                     \
-    } else {                                                                                    \
-      ShadeDiffLaneFn<NL, false, G, F, LGV> fn{{(const float4 *)drgba, nullptr, nullptr, 0.0f, ids, (const F3 *)bary, corners,  \
-                                                recs, lights, LGV ? light_rows : nullptr, T, W, H, transforms, empty_regions}, fold_recs};                         \
-      rc = launch_accumulate_lanes(fn, B, T, W, H, acc, s);                                     \
-    }                                                                                           \
-  }
-#define MR_SHADE_DIFF(NL, G, F) MR_SHADE_DIFF_LG(NL, G, F, false)
-#define MR_SHADE_DIFF_GV(NL, LGV)                                                               \
-  if (folded) {                                                                                 \
-    if (groups == 2) MR_SHADE_DIFF_LG(NL, 2, true, LGV) else if (groups == 3) MR_SHADE_DIFF_LG(NL, 3, true, LGV) else MR_SHADE_DIFF_LG(NL, 7, true, LGV) \
-  } else {                                                                                      \
-    if (groups == 2) MR_SHADE_DIFF_LG(NL, 2, false, LGV) else if (groups == 3) MR_SHADE_DIFF_LG(NL, 3, false, LGV) else MR_SHADE_DIFF_LG(NL, 7, false, LGV) \
-  }
-#define MR_SHADE_DIFF_G(NL) MR_SHADE_DIFF_GV(NL, false)
-#define MR_SHADE_DIFF_GL(NL)   /* one or two lights: the variant with light gradients exists */ \
-  if (light_grads) { MR_SHADE_DIFF_GV(NL, true) } else { MR_SHADE_DIFF_GV(NL, false) }
-    switch (L) {
-      case 1: MR_SHADE_DIFF_GL(1); break;
-      case 2: MR_SHADE_DIFF_GL(2); break;
-      case 3: MR_SHADE_DIFF_G(3); break;
-      case 4: MR_SHADE_DIFF_G(4); break;
-      default: MR_SHADE_DIFF_G(0); break;
-    }
-#undef MR_SHADE_DIFF_GL
-#undef MR_SHADE_DIFF_G
-#undef MR_SHADE_DIFF_GV
-#undef MR_SHADE_DIFF
-#undef MR_SHADE_DIFF_LG
-  } else if (use_lanes) {
-    switch (L) {
-      case 1: MR_SHADE_LANES_GL(1); break;
-      case 2: MR_SHADE_LANES_GL(2); break;
-      case 3: MR_SHADE_LANES_G(3); break;
-      case 4: MR_SHADE_LANES_G(4); break;
-      default: MR_SHADE_LANES_G(0); break;  // 5..kMaxLightsAny lights: run-time loop
-    }
-  } else {
-#define MR_SHADE_BWD(NL)                                                                        \
-  {                                                                                             \
-    KernelTimer timer(MR_TIMER_SHADE_BACKWARD, s);                                              \
-    if (signs && light_grads) {                                                                 \
-      ShadeGradFn<NL, true, true> fn{nullptr, signs, sign_upstream, sign_inv_n, ids, (const F3 *)bary, corners, \
-                                     recs, lights, light_rows, T, W, H};                        \
-      rc = launch_accumulate_rows(fn, B, T, W, H, acc, s, det ? det_block : nullptr);           \
-    } else if (signs) {                                                                         \
-      ShadeGradFn<NL, true, false> fn{nullptr, signs, sign_upstream, sign_inv_n, ids, (const F3 *)bary, corners, \
-                                      recs, lights, nullptr, T, W, H};                          \
-      rc = launch_accumulate_rows(fn, B, T, W, H, acc, s, det ? det_block : nullptr);           \
-    } else if (light_grads) {                                                                   \
-      ShadeGradFn<NL, false, true> fn{(const float4 *)drgba, nullptr, nullptr, 0.0f, ids, (const F3 *)bary, \
-                                      corners, recs, lights, light_rows, T, W, H};              \
-      rc = launch_accumulate_rows(fn, B, T, W, H, acc, s, det ? det_block : nullptr);           \
-    } else {                                                                                    \
-      ShadeGradFn<NL, false, false> fn{(const float4 *)drgba, nullptr, nullptr, 0.0f, ids, (const F3 *)bary, \
-                                       corners, recs, lights, nullptr, T, W, H};                \
-      rc = launch_accumulate_rows(fn, B, T, W, H, acc, s, det ? det_block : nullptr);           \
-    }                                                                                           \
-  }
-  switch (L) {
-    case 1: MR_SHADE_BWD(1); break;
-    case 2: MR_SHADE_BWD(2); break;
-    case 3: MR_SHADE_BWD(3); break;
-    case 4: MR_SHADE_BWD(4); break;
-    default: {  // 5..kMaxLightsAny lights: run-time loop, no light gradients (rejected above)
-      KernelTimer timer(MR_TIMER_SHADE_BACKWARD, s);
-      if (signs) {
-        ShadeGradFn<0, true, false> fn{nullptr, signs, sign_upstream, sign_inv_n, ids, (const F3 *)bary, corners,
-                                       recs, lights, nullptr, T, W, H};
-        rc = launch_accumulate_rows(fn, B, T, W, H, acc, s, det ? det_block : nullptr);
-      } else {
-        ShadeGradFn<0, false, false> fn{(const float4 *)drgba, nullptr, nullptr, 0.0f, ids, (const F3 *)bary,
-                                        corners, recs, lights, nullptr, T, W, H};
-        rc = launch_accumulate_rows(fn, B, T, W, H, acc, s, det ? det_block : nullptr);
-      }
-    } break;
-  }
-  }
-#undef MR_SHADE_BWD
-#undef MR_SHADE_LANES_G
-#undef MR_SHADE_LANES
-#undef MR_SHADE_LANES_FOLDED
   if (rc != MR_OK) return rc;
   if (light_grads) {  // the strips' rows of light sums -> [B][6L + 3], fixed order (every element is written)
-    rc = launch_sum_strip_rows(light_rows, B, light_strips_per_image(B, W, H, use_lanes), L * 6 + 3, light_grads, s);
+    rc = launch_sum_strip_rows(light_rows, B, light_strips_per_image(B, W, H, plan.pixel != ShadePixelPass::kRows), L * 6 + 3,
+                               light_grads, s);
     if (rc != MR_OK) return rc;
   }
-  if (fold_diff) {  // compact rows, position gradient only
-    const long nbv = (long)B * V * 4;
-    // (a `prepared` block's rows are left dirty: it serves ONE backward call.  A gather that zeroes what it reads --
-    //  k_shade_gather_fold<true> -- would let a block serve any number of calls, but its scattered 4-byte stores
-    //  took the gather from 12.7 to 22.3 us; the host side falls back to this call's own setup kernel instead when
-    //  a retained graph is differentiated a second time.)
-    hipLaunchKernelGGL(k_shade_gather_fold<false>, dim3((unsigned)((nbv + kThreads - 1) / kThreads)), dim3(kThreads), 0, s,
-                       acc, vertex_offsets, vertex_entries, B, V, T, dpositions, signs ? sign_upstream : nullptr, sign_inv_n);
-    return check_launch();
+  switch (plan.vertex) {
+    case ShadeVertexPass::kGatherFold: {  // compact rows, position gradient only
+      const long nbv = (long)B * V * 4;
+      // (a `prepared` block's rows are left dirty: it serves ONE backward call.  A gather that zeroes what it reads --
+      //  k_shade_gather_fold<true> -- would let a block serve any number of calls, but its scattered 4-byte stores
+      //  took the gather from 12.7 to 22.3 us; the host side falls back to this call's own setup kernel instead when
+      //  a retained graph is differentiated a second time.)
+      hipLaunchKernelGGL(k_shade_gather_fold<false>, dim3((unsigned)((nbv + kThreads - 1) / kThreads)), dim3(kThreads), 0, s,
+                         acc, vertex_offsets, vertex_entries, B, V, T, dpositions, signs ? sign_upstream : nullptr, sign_inv_n);
+    } break;
+    case ShadeVertexPass::kGather: {
+      const long nbv = (long)B * V * 16;  // sixteen lanes per vertex
+      const dim3 grid((unsigned)((nbv + kThreads - 1) / kThreads));
+      static_switch(det, [&](auto fixed) {
+        hipLaunchKernelGGL(k_shade_gather<decltype(fixed)::value>, grid, dim3(kThreads), 0, s, acc, det_block, vertex_offsets,
+                           vertex_entries, B, V, T, dnormals, dpositions, ddiffuse, dclip, transforms);
+        return MR_OK;
+      });
+    } break;
+    default: {   // no adjacency: atomics per touched (image, triangle)
+      const long nbt = (long)B * T;
+      hipLaunchKernelGGL(k_shade_scatter, dim3((unsigned)((nbt + kThreads - 1) / kThreads)),
+                         dim3(kThreads), 0, s, acc, tris, B, V, T, dnormals, dpositions, ddiffuse, dclip);
+    } break;
   }
-  if (vertex_offsets && vertex_entries) {
-    const long nbv = (long)B * V * 16;  // sixteen lanes per vertex
-    const dim3 grid((unsigned)((nbv + kThreads - 1) / kThreads));
-    if (det) {
-      hipLaunchKernelGGL(k_shade_gather<true>, grid, dim3(kThreads), 0, s, acc, det_block, vertex_offsets,
-                         vertex_entries, B, V, T, dnormals, dpositions, ddiffuse, dclip, transforms);
-    } else {
-      hipLaunchKernelGGL(k_shade_gather<false>, grid, dim3(kThreads), 0, s, acc, det_block, vertex_offsets,
-                         vertex_entries, B, V, T, dnormals, dpositions, ddiffuse, dclip, transforms);
-    }
-    return check_launch();
-  }
-  const long nbt = (long)B * T;
-  hipLaunchKernelGGL(k_shade_scatter, dim3((unsigned)((nbt + kThreads - 1) / kThreads)),
-                     dim3(kThreads), 0, s, acc, tris, B, V, T, dnormals, dpositions, ddiffuse, dclip);
   return check_launch();
 }
 

@@ -1153,6 +1153,8 @@ int launch_spec_corner_setup(const float *normals, const float *positions, const
   return check_launch();
 }
 
+constexpr std::integer_sequence<int, 1, 2, 3, 4> kSpecLights{};   // light counts the kernels are instantiated for
+
 // sums: [B,L] out (kNorms, kGsum), through `partials` (spec_partials_bytes() of scratch)
 template <int PASS, bool PV>
 int launch_spec_pixels(int L, const int32_t *ids, const float *bary, const void *corners,
@@ -1161,19 +1163,12 @@ int launch_spec_pixels(int L, const int32_t *ids, const float *bary, const void 
   const int x_blocks = (W + kThreads - 1) / kThreads;
   const int y_blocks = (H + kSpecRows - 1) / kSpecRows;
   const dim3 grid((unsigned)((size_t)x_blocks * y_blocks * B)), block(kThreads);
-#define MR_SPEC_PIXELS(NL)                                                                        \
-  hipLaunchKernelGGL((k_spec_pixels<NL, PASS, PV>), grid, block, 0, s, ids, (const F3 *)bary,     \
-                     (const SpecCornerRec<attr_count(PV)> *)corners, scene, T, W, H, x_blocks,    \
-                     y_blocks, (const float4 *)drgba, (float4 *)rgba, partials)
-  switch (L) {
-    case 1: MR_SPEC_PIXELS(1); break;
-    case 2: MR_SPEC_PIXELS(2); break;
-    case 3: MR_SPEC_PIXELS(3); break;
-    case 4: MR_SPEC_PIXELS(4); break;
-    default: return MR_EINVAL;
-  }
-#undef MR_SPEC_PIXELS
-  const int rc = check_launch();
+  const int rc = static_switch(L, kSpecLights, [&](auto nl) {
+    hipLaunchKernelGGL((k_spec_pixels<decltype(nl)::value, PASS, PV>), grid, block, 0, s, ids, (const F3 *)bary,
+                       (const SpecCornerRec<attr_count(PV)> *)corners, scene, T, W, H, x_blocks, y_blocks,
+                       (const float4 *)drgba, (float4 *)rgba, partials);
+    return check_launch();
+  });
   if (rc != MR_OK || PASS == kShade) return rc;
   hipLaunchKernelGGL(k_spec_sum, dim3((unsigned)B), dim3(kThreads), 0, s, partials, spec_blocks_per_image(W, H), L,
                      sums);
@@ -1207,6 +1202,44 @@ inline size_t spec_light_rows_bytes(int B, int W, int H) {
   return align_up((rows_kernel > lanes_g ? rows_kernel : lanes_g) * sizeof(float), 256);
 }
 
+// The backward's workspace: the byte offset of every sub-buffer, in this order, and their sum; behind it, for
+// mr_shade_specular_backward_l1, the dense upstream image of the pixel kernels that do not read sign codes.
+struct SpecBackwardLayout {
+  size_t acc, recs, corners, gsum, partials, light_rows, det_block, fold_recs, total, dense, total_l1;
+};
+SpecBackwardLayout spec_backward_layout(int B, int T, int W, int H) {
+  SpecBackwardLayout l{};
+  const auto take = [&l](size_t bytes) { const size_t offset = l.total; l.total += bytes; return offset; };
+  l.acc = take(spec_acc_bytes(B, T));
+  l.recs = take(align_up((size_t)B * T * sizeof(BwdRec), 256));
+  l.corners = take(spec_corner_bytes(B, T));
+  l.gsum = take(spec_sums_bytes(B));
+  l.partials = take(spec_partials_bytes(B, W, H));
+  l.light_rows = take(spec_light_rows_bytes(B, W, H));
+  l.det_block = take(kDetBlockBytes);
+  l.fold_recs = take(align_up((size_t)B * T * sizeof(SpecFoldRec<kAttrMax>), 256));
+  l.dense = align_up(l.total, 256);
+  l.total_l1 = l.dense + align_up((size_t)B * H * W * 4 * sizeof(float), 256);
+  return l;
+}
+
+// Which pixel pass runs.  MR_SPEC_LANES / MR_SPEC_COUPLED: compile-time A/B switches.
+struct SpecBackwardPlan {
+  bool lanes;        // SpecFoldLaneFn: vertex gradients only, a normalised G-buffer, float atomics
+  bool fold;         // ... with the pull-back through the transforms folded in (no clip-space gradient wanted)
+  bool coupled;      // SpecCoupledLaneFn: one pass instead of G pass + pixel pass -- one or two lights, folded, per-vertex gather
+  bool dense_first;  // sign codes, but only the coupled kernel reads them: the loss's backward forms the dense image first
+};
+SpecBackwardPlan plan_spec_backward(int L, bool signs, int grads_wanted, bool normalised, bool transforms, bool adjacency,
+                                    bool deterministic) {
+  SpecBackwardPlan p;
+  p.lanes = MR_SPEC_LANES && !deterministic && normalised && (grads_wanted & ~(MR_GRAD_POSITIONS | MR_GRAD_CLIP)) == 0;
+  p.fold = p.lanes && transforms && (grads_wanted & MR_GRAD_CLIP) == 0;
+  p.coupled = MR_SPEC_COUPLED && p.fold && L <= 2 && adjacency;
+  p.dense_first = signs && !p.coupled;
+  return p;
+}
+
 template <bool PV>
 int spec_backward(const float *drgba, const uint8_t *signs, const float *sign_upstream, const int32_t *ids, const float *bary, const float *clip,
                   const float *normals, const float *positions, const float *diffuse, const float *specular,
@@ -1218,134 +1251,96 @@ int spec_backward(const float *drgba, const uint8_t *signs, const float *sign_up
                   void *ws, hipStream_t s) {
   constexpr int A = attr_count(PV);
   const bool det = g_deterministic != 0;
-  // the lane kernel (SpecFoldLaneFn): vertex gradients only, a normalised G-buffer, float atomics
-  const bool lanes = MR_SPEC_LANES && !det && (gbuffer_flags & MR_GBUFFER_NORMALISED) != 0 &&
-                     (grads_wanted & ~(MR_GRAD_POSITIONS | MR_GRAD_CLIP)) == 0;
-  const bool fold = lanes && transforms && (grads_wanted & MR_GRAD_CLIP) == 0;
-  // one pass instead of G pass + pixel pass (SpecCoupledLaneFn): one or two lights, folded, per-vertex gather
-  const bool coupled = MR_SPEC_COUPLED && fold && L <= 2 && vertex_offsets && vertex_entries;
-  if (det && !(vertex_offsets && vertex_entries)) return MR_EINVAL;  // the scatter path is float atomics only
+  const bool adjacency = vertex_offsets && vertex_entries;
+  if (det && !adjacency) return MR_EINVAL;  // the scatter path is float atomics only
+  const SpecBackwardPlan plan = plan_spec_backward(L, signs != nullptr, grads_wanted, (gbuffer_flags & MR_GBUFFER_NORMALISED) != 0,
+                                                   transforms != nullptr, adjacency, det);
+  const SpecBackwardLayout at = spec_backward_layout(B, T, W, H);
+  char *const base = (char *)ws;
   const size_t n_image = (size_t)B * H * W * 4;
   const float sign_inv_n = 1.0f / (float)n_image;
-  if (signs && !coupled) {  // the other pixel kernels take the dense image: the loss's backward, into the workspace's tail
-    float *dense = (float *)((char *)ws + align_up(shade_specular_backward_ws(B, V, T, W, H), 256));
+  if (plan.dense_first) {
+    float *dense = (float *)(base + at.dense);
     const int rc_l1 = launch_l1_backward(signs, n_image, sign_upstream, dense, s);
     if (rc_l1 != MR_OK) return rc_l1;
     drgba = dense;
     signs = nullptr;
   }
-  char *p = (char *)ws;
-  float *acc = (float *)p;
-  p += spec_acc_bytes(B, T);
-  BwdRec *recs = (BwdRec *)p;
-  p += align_up((size_t)B * T * sizeof(BwdRec), 256);
-  void *corners = p;
-  p += spec_corner_bytes(B, T);
-  float *gsum = (float *)p;
-  p += spec_sums_bytes(B);
-  float *partials = (float *)p;
-  p += spec_partials_bytes(B, W, H);
-  float *light_rows = (float *)p;
-  p += spec_light_rows_bytes(B, W, H);
-  DetBlock *det_block = (DetBlock *)p;
-  p += kDetBlockBytes;
-  SpecFoldRec<A> *fold_recs = (SpecFoldRec<A> *)p;
+  float *acc = (float *)(base + at.acc);
+  BwdRec *recs = (BwdRec *)(base + at.recs);
+  void *corners = base + at.corners;
+  float *gsum = (float *)(base + at.gsum);
+  float *partials = (float *)(base + at.partials);
+  float *light_rows = (float *)(base + at.light_rows);
+  DetBlock *det_block = (DetBlock *)(base + at.det_block);
+  SpecFoldRec<A> *fold_recs = (SpecFoldRec<A> *)(base + at.fold_recs);
   if (zero_async(acc, (size_t)B * T * 48 * (det ? sizeof(long long) : sizeof(float)), s) != hipSuccess)
     return check_launch();
   int rc = MR_OK;
   if (det && (rc = launch_det_scale(drgba, (size_t)B * H * W * 4, 1.0f, det_block, s)) != MR_OK) return rc;
-  if (!lanes) {
+  if (!plan.lanes) {
     rc = launch_bwd_setup(clip, tris, B, V, T, recs, s);
     if (rc != MR_OK) return rc;
   }
   rc = launch_spec_corner_setup<PV>(normals, positions, diffuse, specular, PV ? shininess : nullptr, tris, B, V, T,
                                     corners, s);
   if (rc != MR_OK) return rc;
-  if (lanes) {
+  if (plan.lanes) {
     const long nbt = (long)B * T;
     hipLaunchKernelGGL((k_spec_fold_setup<A>), dim3((unsigned)((nbt + kThreads - 1) / kThreads)), dim3(kThreads), 0, s,
                        (const float4 *)clip, tris, (const SpecCornerRec<A> *)corners, B, V, T, fold_recs,
-                       coupled ? transforms : nullptr);
+                       plan.coupled ? transforms : nullptr);
     if ((rc = check_launch()) != MR_OK) return rc;
   }
   SpecSceneIn scene{light_pos, light_col, ambient, camera, PV ? nullptr : shininess, norms2, nullptr};
-  if (coupled) {
-#define MR_SPEC_BWD_COUPLED(NL, SG)                                                                                  \
-    {                                                                                                                \
-      SpecCoupledLaneFn<NL, PV, SG> fn{{(const float4 *)drgba, ids, (const F3 *)bary, nullptr, nullptr, scene, nullptr, T, W, H, \
-                                        signs}, fold_recs, light_rows};                                              \
-      rc = launch_accumulate_lanes(fn, B, T, W, H, acc, s);                                                          \
-      if (rc == MR_OK)                                                                                               \
-        rc = launch_sum_strip_rows(light_rows, B, lanes_strips_per_image<SpecCoupledLaneFn<NL, PV, SG>>(B, W, H), NL, gsum, s); \
-      if (rc == MR_OK) {                                                                                             \
-        const long nbv4 = (long)B * V * 4;                                                                           \
-        hipLaunchKernelGGL((k_spec_gather_coupled<A, NL>), dim3((unsigned)((nbv4 + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, \
-                           acc, vertex_offsets, vertex_entries, gsum, norms2, B, V, T, dpositions,                   \
-                           SG ? sign_upstream : nullptr, sign_inv_n);                                                \
-        rc = check_launch();                                                                                         \
-      }                                                                                                              \
-    }
-    if (signs) {
-      if (L == 1) MR_SPEC_BWD_COUPLED(1, true) else MR_SPEC_BWD_COUPLED(2, true)
-    } else {
-      if (L == 1) MR_SPEC_BWD_COUPLED(1, false) else MR_SPEC_BWD_COUPLED(2, false)
-    }
-#undef MR_SPEC_BWD_COUPLED
-    return rc;
-  }
+  if (plan.coupled)
+    return static_switch(L, std::integer_sequence<int, 1, 2>{}, [&](auto nl) {
+      return static_switch(signs != nullptr, [&](auto sign_codes) {
+        constexpr int NL = decltype(nl)::value;
+        constexpr bool SG = decltype(sign_codes)::value;
+        const SpecCoupledLaneFn<NL, PV, SG> fn{{(const float4 *)drgba, ids, (const F3 *)bary, nullptr, nullptr, scene, nullptr,
+                                                T, W, H, signs}, fold_recs, light_rows};
+        int rc = launch_accumulate_lanes(fn, B, T, W, H, acc, s);
+        if (rc != MR_OK) return rc;
+        rc = launch_sum_strip_rows(light_rows, B, lanes_strips_per_image<SpecCoupledLaneFn<NL, PV, SG>>(B, W, H), NL, gsum, s);
+        if (rc != MR_OK) return rc;
+        const long nbv4 = (long)B * V * 4;
+        hipLaunchKernelGGL((k_spec_gather_coupled<A, NL>), dim3((unsigned)((nbv4 + kThreads - 1) / kThreads)), dim3(kThreads), 0, s,
+                           acc, vertex_offsets, vertex_entries, gsum, norms2, B, V, T, dpositions,
+                           SG ? sign_upstream : nullptr, sign_inv_n);
+        return check_launch();
+      });
+    });
   rc = launch_spec_pixels<kGsum, PV>(L, ids, bary, corners, scene, B, T, W, H, drgba, nullptr, gsum, partials, s);
   if (rc != MR_OK) return rc;
   scene.gsum = gsum;
-#define MR_SPEC_BWD(NL)                                                                               \
-  {                                                                                                   \
-    SpecGradFn<NL, PV> fn{(const float4 *)drgba, ids, (const F3 *)bary, (const SpecCornerRec<A> *)corners, \
-                          recs, scene, light_rows, T, W, H};                                          \
-    rc = launch_accumulate_rows(fn, B, T, W, H, acc, s, det ? det_block : nullptr);                   \
-  }
-#define MR_SPEC_BWD_LANES(NL, FOLDED)                                                                    \
-  {                                                                                                      \
-    SpecFoldLaneFn<NL, PV, FOLDED> fn{{(const float4 *)drgba, ids, (const F3 *)bary, nullptr, nullptr, scene, \
-                                       nullptr, T, W, H}, fold_recs, transforms};                        \
-    rc = launch_accumulate_lanes(fn, B, T, W, H, acc, s);                                                \
-  }
-  if (lanes) {   // (the image-wide sums are not wanted: light_grads stays as the caller's launcher cleared it)
-    switch (L * 2 + (fold ? 1 : 0)) {
-      case 2: MR_SPEC_BWD_LANES(1, false); break;
-      case 3: MR_SPEC_BWD_LANES(1, true); break;
-      case 4: MR_SPEC_BWD_LANES(2, false); break;
-      case 5: MR_SPEC_BWD_LANES(2, true); break;
-      case 6: MR_SPEC_BWD_LANES(3, false); break;
-      case 7: MR_SPEC_BWD_LANES(3, true); break;
-      case 8: MR_SPEC_BWD_LANES(4, false); break;
-      case 9: MR_SPEC_BWD_LANES(4, true); break;
-      default: return MR_EINVAL;
+  rc = static_switch(L, kSpecLights, [&](auto nl) {
+    constexpr int NL = decltype(nl)::value;
+    if (!plan.lanes) {
+      const SpecGradFn<NL, PV> fn{(const float4 *)drgba, ids, (const F3 *)bary, (const SpecCornerRec<A> *)corners,
+                                  recs, scene, light_rows, T, W, H};
+      return launch_accumulate_rows(fn, B, T, W, H, acc, s, det ? det_block : nullptr);
     }
-  } else {
-    switch (L) {
-      case 1: MR_SPEC_BWD(1); break;
-      case 2: MR_SPEC_BWD(2); break;
-      case 3: MR_SPEC_BWD(3); break;
-      case 4: MR_SPEC_BWD(4); break;
-      default: return MR_EINVAL;
-    }
-  }
-#undef MR_SPEC_BWD
-#undef MR_SPEC_BWD_LANES
+    // (the image-wide sums are not wanted: light_grads stays as the caller's launcher cleared it)
+    return static_switch(plan.fold, [&](auto folded) {
+      const SpecFoldLaneFn<NL, PV, decltype(folded)::value> fn{{(const float4 *)drgba, ids, (const F3 *)bary, nullptr, nullptr, scene,
+                                                                nullptr, T, W, H}, fold_recs, transforms};
+      return launch_accumulate_lanes(fn, B, T, W, H, acc, s);
+    });
+  });
   if (rc != MR_OK) return rc;
-  if (!lanes) {
+  if (!plan.lanes) {
     rc = launch_sum_strip_rows(light_rows, B, strips_per_image<SpecGradFn<1, PV>>(W, H), L * 6 + 7, light_grads, s);
     if (rc != MR_OK) return rc;
   }
-  if (vertex_offsets && vertex_entries) {
+  if (adjacency) {
     const long nbv = (long)B * V * 16;  // sixteen lanes per vertex
     const dim3 grid((unsigned)((nbv + kThreads - 1) / kThreads));
-    if (det)
-      hipLaunchKernelGGL((k_spec_gather<A, true>), grid, dim3(kThreads), 0, s, acc, det_block, vertex_offsets,
+    return static_switch(det, [&](auto fixed) {
+      hipLaunchKernelGGL((k_spec_gather<A, decltype(fixed)::value>), grid, dim3(kThreads), 0, s, acc, det_block, vertex_offsets,
                          vertex_entries, B, V, T, dnormals, dpositions, ddiffuse, dspecular, dshininess, dclip);
-    else
-      hipLaunchKernelGGL((k_spec_gather<A, false>), grid, dim3(kThreads), 0, s, acc, det_block, vertex_offsets,
-                         vertex_entries, B, V, T, dnormals, dpositions, ddiffuse, dspecular, dshininess, dclip);
-    return check_launch();
+      return check_launch();
+    });
   }
   const long nbt = (long)B * T;
   hipLaunchKernelGGL((k_spec_scatter<A>), dim3((unsigned)((nbt + kThreads - 1) / kThreads)), dim3(kThreads), 0, s,
@@ -1377,14 +1372,12 @@ int launch_shade_specular_forward(const int32_t *ids, const float *bary, const f
 
 size_t shade_specular_backward_ws(int B, int V, int T, int W, int H) {
   (void)V;
-  return spec_acc_bytes(B, T) + align_up((size_t)B * T * sizeof(BwdRec), 256) + spec_corner_bytes(B, T) +
-         spec_sums_bytes(B) + spec_partials_bytes(B, W, H) + spec_light_rows_bytes(B, W, H) + kDetBlockBytes +
-         align_up((size_t)B * T * sizeof(SpecFoldRec<kAttrMax>), 256);
+  return spec_backward_layout(B, T, W, H).total;
 }
 
 size_t shade_specular_backward_l1_ws(int B, int V, int T, int W, int H) {
-  // + the dense upstream image for the pixel kernels that do not read sign codes
-  return align_up(shade_specular_backward_ws(B, V, T, W, H), 256) + align_up((size_t)B * H * W * 4 * sizeof(float), 256);
+  (void)V;
+  return spec_backward_layout(B, T, W, H).total_l1;
 }
 
 int launch_shade_specular_backward(const float *drgba, const uint8_t *signs, const float *sign_upstream,

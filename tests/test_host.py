@@ -73,6 +73,20 @@ def test_ctypes_signatures_match_the_header():
     assert checked >= 25
 
 
+def test_shading_backward_workspace_sizes_are_pinned():
+    """Callers size their scratch from these and `prepared` blocks are laid out by them: the byte counts of the
+    commit that introduced ShadeBackwardLayout / SpecBackwardLayout's parent, recorded from its build."""
+    L = _native.lib()
+    entries = ("mr_shade_backward_workspace_bytes", "mr_shade_backward_l1_workspace_bytes",
+               "mr_shade_specular_backward_workspace_bytes", "mr_shade_specular_backward_l1_workspace_bytes")
+    pinned = {(1, 8, 12, 32, 24): ((9472, 9728, 11264, 23552), 2816),
+              (2, 642, 1280, 130, 67): ((1670912, 1671168, 2094336, 2373120), 532480),
+              (32, 2502, 5000, 1024, 1024): ((107220480, 107220736, 135279616, 672150528), 33280000)}
+    for (B, V, T, W, H), (workspaces, prepared) in pinned.items():
+        assert tuple(getattr(L, name)(B, V, T, W, H) for name in entries) == workspaces, (B, V, T, W, H)
+        assert L.mr_shade_backward_prepared_bytes(B, T) == prepared, (B, T)
+
+
 def test_abi_argument_validation_without_gpu():
     L = _native.lib()
     # bad sizes are rejected before anything touches a device

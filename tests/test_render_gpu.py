@@ -1187,7 +1187,7 @@ def test_shade_backward_lane_kernel_matches_rows_kernel(device, w, h, res, n_lig
                                                    atol=2e-6 * scale, err_msg="output %d kernel %d" % (k, which))
             # round 4: the clip-space gradient not wanted on its own (render() differentiated to the vertices
             # only): the pull-back through the transforms is folded into the pixel pass -- 9 sums per triangle
-            # (ShadeLaneFn<..., FOLD>) -- and where that variant does not exist (rows kernel forced, G-buffer
+            # (ShadeFoldLaneFn) -- and where that variant does not exist (rows kernel forced, G-buffer
             # not declared normalised, normals wanted) the clip gradient goes to scratch: dclip is None and
             # d positions is the same whole-vertex gradient every time
             scale = float(full[2].abs().max())
