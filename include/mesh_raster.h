@@ -226,6 +226,32 @@ int mr_render_forward(const float *vertices, const float *transforms, const floa
                       uint8_t *rgba_u8, void *corner_records, void *backward_prepared, uint8_t *empty_regions,
                       void *workspace, size_t workspace_bytes, void *stream);
 
+/* mr_render_forward, and mean|rgba - target| out of the same pass: the tile walk's epilogue reads the target's
+ * pixel next to the RGBA it is about to store and leaves the loss and its sign codes, so that no loss kernel has to
+ * read the image back (16 B/px less, one dependent launch less).  For a FIXED target (an optimisation loop compares
+ * every step's image with the same one).  Same arguments and outputs as mr_render_forward, then:
+ *   target        [B,H,W,4] f32, 16-byte aligned, image rows like rgba
+ *   target_empty  NULL, or the target's block map (mr_image_empty_regions): a region that is empty on both sides
+ *                 gets zero codes without its target being read (64-pixel regions only; ignored otherwise)
+ *   loss          1 f32 out: sum |rgba - target| / (4 B H W)
+ *   signs         [B*H*W] u8 out: one byte of four 2-bit codes per pixel, exactly as mr_l1_loss_forward writes them
+ *                 (sign(+-0) = sign(NaN) = 0); what mr_shade_backward_l1 and mr_l1_loss_backward take
+ *   partials      scratch, mr_render_forward_l1_partials(B, W, H) floats: one partial sum per region of the
+ *                 rasterizer's walk, added in a fixed order by a second, one-workgroup launch: the loss has the
+ *                 same bits from run to run.
+ * The outputs equal mr_render_forward followed by mr_l1_loss_forward_regions on its image and map, apart from the
+ * grouping of the loss's sum (per region instead of per row: equal to a few units of rounding, 1e-6 relative). */
+size_t mr_render_forward_l1_partials(int B, int W, int H);
+int mr_render_forward_l1(const float *vertices, const float *transforms, const float *normals,
+                         const float *diffuse, const int32_t *triangles,
+                         const float *light_positions, const float *light_intensities,
+                         const float *ambient, int B, int V, int T, int W, int H, int L,
+                         float *clip, int32_t *ids, float *bary, float *z, int want_z, float *rgba,
+                         uint8_t *rgba_u8, void *corner_records, void *backward_prepared, uint8_t *empty_regions,
+                         void *workspace, size_t workspace_bytes, void *stream,
+                         const float *target, const uint8_t *target_empty, float *loss, uint8_t *signs,
+                         float *partials);
+
 /* Backward of mr_shade_forward AND of the rasterizer underneath it, in one pass
  * over the G-buffer (reads 32 B/px).  All outputs are zeroed here.
  *   drgba        [B,H,W,4] f32  dL/d(rgba); the alpha channel's gradient is ignored
@@ -727,6 +753,11 @@ int mr_set_deterministic(int on);
 #define MR_TIMER_L1_FORWARD 4      /* the streaming pass of mr_l1_loss_forward                        */
 #define MR_TIMER_COUNT 5
 int mr_time_next_kernel(int which, void *start_event, void *stop_event);
+/* The named kernel will NOT run in this step after all (mean|image - target| came out of mr_render_forward_l1): the
+ * calling thread's armed pair, if any, is recorded on `stream` back to back -- an empty interval, so that a reader
+ * of the pair finds two recorded events and a time of (nearly) zero instead of events that never happened, and the
+ * pair does not wait for some later launch of that kernel -- and the slot clears. */
+int mr_time_no_kernel(int which, void *stream);
 
 #ifdef __cplusplus
 }

@@ -108,6 +108,19 @@ def _arm_timer(which):
         lib().mr_time_next_kernel(which, pair[0], pair[1])
 
 
+def close_pending_timer(which, dev):
+    """A pair handed to time_next_kernel whose kernel will not run in this step (the loss that the fused forward already
+    computed): left pending, it would bracket some LATER launch of that kernel and be read as this step's.  It is
+    recorded back to back on the current stream instead -- an empty interval: whoever reads the pair finds recorded
+    events and (nearly) zero, not events that never happened (hipEventElapsedTime fails on those, and the error stays
+    behind as the thread's last HIP error for the next caller that looks)."""
+    pair = _pending_timers.pop(which, None)
+    if pair is not None:
+        with torch.cuda.device(dev):
+            lib().mr_time_next_kernel(which, pair[0], pair[1])
+            lib().mr_time_no_kernel(which, _stream(dev))
+
+
 
 class NativeLibraryError(RuntimeError):
     pass
@@ -286,6 +299,16 @@ def lib():
             L.mr_attribute_derivatives.restype = ci
         except AttributeError as e:   # the texture entry points came without an ABI version bump
             raise NativeLibraryError("%s lacks the texture entry points (%s): rebuild it (make -C "
+                                     "pytorch_mesh_renderer_amd/csrc)" % (LIB_PATH, e))
+        try:
+            L.mr_render_forward_l1_partials.argtypes = [ci] * 3
+            L.mr_render_forward_l1_partials.restype = sz
+            L.mr_render_forward_l1.argtypes = L.mr_render_forward.argtypes + [vp] * 5
+            L.mr_render_forward_l1.restype = ci
+            L.mr_time_no_kernel.argtypes = [ci, vp]
+            L.mr_time_no_kernel.restype = ci
+        except AttributeError as e:   # the loss-in-forward entry points came without an ABI version bump
+            raise NativeLibraryError("%s lacks mr_render_forward_l1 (%s): rebuild it (make -C "
                                      "pytorch_mesh_renderer_amd/csrc)" % (LIB_PATH, e))
         try:
             L.mr_mesh_regularizer_workspace_bytes.argtypes = [ci] * 3
@@ -565,7 +588,8 @@ def vertex_transform(vertices, transforms):
 
 
 def render_forward(vertices, transforms, normals, diffuse, triangles, light_positions, light_intensities,
-                   ambient, width, height, want_z=True, want_u8=False, prepare_backward=False, want_empty_regions=False):
+                   ambient, width, height, want_z=True, want_u8=False, prepare_backward=False, want_empty_regions=False,
+                   l1_target=None, l1_target_empty=None):
     """render()'s forward from world-space vertices: clip-space transform, rasterizer and shading
     (the shading is the epilogue of the rasterizer's tile walk: one pass over the pixels)
     -> (clip, ids, bary, z, rgba, corner_records); with want_z=False the depth plane is not written
@@ -578,7 +602,12 @@ def render_forward(vertices, transforms, normals, diffuse, triangles, light_posi
 
     want_empty_regions=True: a [B, ceil(H/64), ceil(W/64)] uint8 map follows the optional frames (before the
     prepared block): 1 = that 64 x 64 block of the G-buffer holds no candidate triangle (background / transparent
-    black); l1_loss_forward(..., empty_a=, empty_b=) and shade_backward(..., empty_regions=) skip such blocks."""
+    black); l1_loss_forward(..., empty_a=, empty_b=) and shade_backward(..., empty_regions=) skip such blocks.
+
+    l1_target ([B,H,W,4] float32, contiguous; mr_render_forward_l1): the same pass also compares every pixel it shades
+    with the target -- the very LAST value is then (loss, signs), what l1_loss_forward(rgba, l1_target) returns (the
+    sum is grouped by region instead of by row: equal to rounding), and no loss kernel has to read the image back.
+    l1_target_empty: the target's image_empty_regions map or None; regions empty on both sides are not read."""
     tensors = [vertices, transforms, normals, diffuse, triangles, light_positions, light_intensities]
     _chk("vertices", vertices, _F32, None, None, 3)
     _chk("triangles", triangles, _I32, None, 3)
@@ -588,6 +617,13 @@ def render_forward(vertices, transforms, normals, diffuse, triangles, light_posi
         _chk(name, t, _F32, B, V, 3)
     _chk_lights(light_positions, light_intensities, ambient, B, shade_max_lights())
     dev = _require_device(*(tensors + ([ambient] if ambient is not None else [])))
+    if l1_target is not None:
+        _chk("l1_target", l1_target, _F32, B, height, width, 4)
+        if l1_target_empty is not None:
+            _chk("l1_target_empty", l1_target_empty, _U8, B, (height + 63) // 64, (width + 63) // 64)
+        if not l1_target.is_contiguous() or (l1_target_empty is not None and not l1_target_empty.is_contiguous()):
+            raise ValueError("l1_target and its map must be contiguous")
+        _require_device(vertices, l1_target, *([l1_target_empty] if l1_target_empty is not None else []))
     L = lib()
     vertices, transforms, normals, diffuse, triangles, light_positions, light_intensities = [
         t.contiguous() for t in tensors]
@@ -607,14 +643,24 @@ def render_forward(vertices, transforms, normals, diffuse, triangles, light_posi
         need = L.mr_rasterize_forward_workspace_bytes(B, V, T, width, height)
         ws, have = _workspace(dev, need)
         _arm_timer(TIMER_RASTER_FORWARD)
-        rc = L.mr_render_forward(_ptr(vertices), _ptr(transforms), _ptr(normals), _ptr(diffuse), _ptr(triangles),
-                                 _ptr(light_positions), _ptr(light_intensities), _ptr(ambient), B, V, T,
-                                 width, height, nl, _ptr(clip), _ptr(ids), _ptr(bary), _ptr(z), int(bool(want_z)),
-                                 _ptr(rgba), _ptr(frames), _ptr(records), _ptr(prepared), _ptr(empty), _ptr(ws), have,
-                                 _stream(dev))
+        args = (_ptr(vertices), _ptr(transforms), _ptr(normals), _ptr(diffuse), _ptr(triangles),
+                _ptr(light_positions), _ptr(light_intensities), _ptr(ambient), B, V, T,
+                width, height, nl, _ptr(clip), _ptr(ids), _ptr(bary), _ptr(z), int(bool(want_z)),
+                _ptr(rgba), _ptr(frames), _ptr(records), _ptr(prepared), _ptr(empty), _ptr(ws), have,
+                _stream(dev))
+        l1 = None
+        if l1_target is None:
+            rc = L.mr_render_forward(*args)
+        else:
+            loss = torch.empty((), dtype=torch.float32, device=dev)
+            signs = torch.empty(B * height * width, dtype=torch.uint8, device=dev)
+            partials = torch.empty(max(1, L.mr_render_forward_l1_partials(B, width, height)), dtype=torch.float32, device=dev)
+            rc = L.mr_render_forward_l1(*args, _ptr(l1_target), _ptr(l1_target_empty), _ptr(loss), _ptr(signs), _ptr(partials))
+            l1 = (loss, signs)
     _check(rc, "mr_render_forward")
     out = (clip, ids, bary, (z if want_z else None), rgba, records) + ((frames,) if want_u8 else ())
-    return out + ((empty,) if want_empty_regions else ()) + ((prepared,) if prepare_backward else ())
+    out = out + ((empty,) if want_empty_regions else ()) + ((prepared,) if prepare_backward else ())
+    return out + ((l1,) if l1 is not None else ())
 
 
 def interpolate_raster_max_attributes():
@@ -1681,15 +1727,21 @@ def soft_backward(drgba, rgba, aux, clip, positions, normals, diffuse, triangles
     return dclip, dp, dn, dd, dlp, dli
 
 
-def image_empty_regions(image):
+def image_empty_regions(image, out=None):
     """[B, ceil(H/64), ceil(W/64)] uint8 map of a [B,H,W,4] float32 device image: 1 = the 64 x 64 block (counted in
     G-buffer rows, i.e. from the image's LAST row up) is whole and all zeros.  What render_forward writes for its own
-    image; l1_loss_forward skips blocks that are empty on both sides."""
+    image; l1_loss_forward skips blocks that are empty on both sides.  out: a map of that shape to overwrite in place."""
     _chk("image", image, _F32, None, None, None, 4)
     dev = _require_device(image)
     image = image.contiguous()
     B, H, W = image.shape[:3]
-    out = torch.empty(B, (H + 63) // 64, (W + 63) // 64, dtype=torch.uint8, device=dev)
+    if out is None:
+        out = torch.empty(B, (H + 63) // 64, (W + 63) // 64, dtype=torch.uint8, device=dev)
+    else:
+        _chk("out", out, _U8, B, (H + 63) // 64, (W + 63) // 64)
+        _require_device(image, out)
+        if not out.is_contiguous():
+            raise ValueError("out must be contiguous")
     with torch.cuda.device(dev):
         rc = lib().mr_image_empty_regions(_ptr(image), B, H, W, _ptr(out), _stream(dev))
     _check(rc, "mr_image_empty_regions")

@@ -51,6 +51,12 @@ int mr_time_next_kernel(int which, void *start_event, void *stop_event) {
   return MR_OK;
 }
 
+int mr_time_no_kernel(int which, void *stream) {
+  if (which < 0 || which >= MR_TIMER_COUNT) return MR_EINVAL;
+  { mr::KernelTimer empty_interval(which, (hipStream_t)stream); }
+  return MR_OK;
+}
+
 // ---- mesh_raster_debug.h ----------------------------------------------------------------
 int mr_debug_set_raster_region_edge(int edge) {
   if (edge != 0 && edge != 32 && edge != 64) return MR_EINVAL;
@@ -277,6 +283,36 @@ int mr_render_forward(const float *vertices, const float *transforms, const floa
                                    light_intensities, ambient, B, V, T, W, H, L, clip, ids, bary, z,
                                    want_z, rgba, rgba_u8, corner_records, backward_prepared, empty_regions, workspace,
                                    (hipStream_t)stream);
+}
+
+size_t mr_render_forward_l1_partials(int B, int W, int H) {
+  if (B < 0 || W < 1 || H < 1 || W > 65535 || H > 65535) return 0;
+  return mr::render_forward_l1_partials(B, W, H);
+}
+
+int mr_render_forward_l1(const float *vertices, const float *transforms, const float *normals,
+                         const float *diffuse, const int32_t *triangles, const float *light_positions,
+                         const float *light_intensities, const float *ambient, int B, int V, int T, int W,
+                         int H, int L, float *clip, int32_t *ids, float *bary, float *z, int want_z,
+                         float *rgba, uint8_t *rgba_u8, void *corner_records, void *backward_prepared,
+                         uint8_t *empty_regions, void *workspace, size_t workspace_bytes, void *stream,
+                         const float *target, const uint8_t *target_empty, float *loss, uint8_t *signs, float *partials) {
+  if (bad_dims(B, V, T, W, H) || T < 1 || V < 1 || L < 1 || L > mr::shade_max_lights())
+    return MR_EINVAL;
+  if (!loss) return MR_EINVAL;
+  if (B == 0) return mr::zero_async(loss, sizeof(float), (hipStream_t)stream) == hipSuccess ? MR_OK : mr::check_launch();
+  if (!vertices || !transforms || !normals || !diffuse || !triangles || !light_positions ||
+      !light_intensities || !clip || !ids || !bary || !z || !rgba || !corner_records ||
+      ((uintptr_t)corner_records & 127u) || ((uintptr_t)clip & 15u) || ((uintptr_t)transforms & 15u) ||
+      ((uintptr_t)rgba_u8 & 3u) || ((uintptr_t)backward_prepared & 255u) ||
+      !target || ((uintptr_t)target & 15u) || !signs || !partials)
+    return MR_EINVAL;
+  const int rc = check_ws(workspace, workspace_bytes, mr::raster_forward_ws(B, V, T, W, H));
+  if (rc != MR_OK) return rc;
+  return mr::launch_render_forward_l1(vertices, transforms, normals, diffuse, triangles, light_positions,
+                                      light_intensities, ambient, B, V, T, W, H, L, clip, ids, bary, z,
+                                      want_z, rgba, rgba_u8, corner_records, backward_prepared, empty_regions, workspace,
+                                      target, target_empty, loss, signs, partials, (hipStream_t)stream);
 }
 
 size_t mr_shade_forward_workspace_bytes(int B, int V, int T, int W, int H) {

@@ -8,6 +8,7 @@
 // signs of a pixel's channels as 2-bit codes) and one backward that never re-reads the images
 // (reads 1 B/px, writes 16 B/px).  Both are HBM-bound; 49 B/px in total instead of 80.
 #include "mr_internal.h"
+#include "l1_code.h"
 
 #ifndef MR_L1_REGIONS_NT_A
 #define MR_L1_REGIONS_NT_A 1   // the image stream of k_l1_forward_regions nontemporal too
@@ -34,9 +35,7 @@ __device__ __forceinline__ float4 nt_load(const float4 *p) {
   return make_float4(v.x, v.y, v.z, v.w);
 }
 
-// 2-bit sign code of d, two's complement: 0 -> 0, 1 -> +1, 3 -> -1 (NaN -> 0, like (0 < d) - (d < 0)); a
-// reader gets the value with one signed bit-field extract (v_bfe_i32) and a conversion.
-__device__ __forceinline__ unsigned sign_code(float d) { return d > 0.f ? 1u : (d < 0.f ? 3u : 0u); }
+// (sign_code, sign_code4, abs_sum4: l1_code.h, shared with the fused forward's epilogue)
 __device__ __forceinline__ float sign_value(unsigned code) {
   return (code & 2u) ? -1.f : ((code & 1u) ? 1.f : 0.f);
 }
@@ -69,10 +68,10 @@ __global__ __launch_bounds__(kThreads) void k_l1_forward(const float4 *__restric
     for (int u = 0; u < kUnroll; ++u) {
       if (u > 0 && j + u * stride >= n4) break;
       const float d0 = x[u].x - y[u].x, d1 = x[u].y - y[u].y, d2 = x[u].z - y[u].z, d3 = x[u].w - y[u].w;
-      s += (fabsf(d0) + fabsf(d1)) + (fabsf(d2) + fabsf(d3));
+      s += abs_sum4(d0, d1, d2, d3);
       if (signs) {
         const uint8_t code =
-            (uint8_t)(sign_code(d0) | (sign_code(d1) << 2) | (sign_code(d2) << 4) | (sign_code(d3) << 6));
+            (uint8_t)sign_code4(d0, d1, d2, d3);
         __builtin_nontemporal_store(code, &signs[idx[u]]);
       }
     }
@@ -357,10 +356,10 @@ __global__ __launch_bounds__(kThreads) void k_l1_forward_regions(
         const int x = x0 + u * kThreads;
         if (x >= W) break;
         const float d0 = va[u].x - vb[u].x, d1 = va[u].y - vb[u].y, d2 = va[u].z - vb[u].z, d3 = va[u].w - vb[u].w;
-        s += (fabsf(d0) + fabsf(d1)) + (fabsf(d2) + fabsf(d3));
+        s += abs_sum4(d0, d1, d2, d3);
         if (signs) {
           const uint8_t code =
-              (uint8_t)(sign_code(d0) | (sign_code(d1) << 2) | (sign_code(d2) << 4) | (sign_code(d3) << 6));
+              (uint8_t)sign_code4(d0, d1, d2, d3);
           __builtin_nontemporal_store(code, &signs[base + x]);
         }
       }
@@ -403,6 +402,13 @@ int launch_l1_forward(const float *a, const float *b, size_t n, float *out, uint
   int rc = check_launch();
   if (rc != MR_OK) return rc;
   hipLaunchKernelGGL(k_l1_finish, dim3(1), dim3(kFinishThreads), 0, s, partials, (int)blocks, out);
+  return check_launch();
+}
+
+// the fixed-order sum of `n` partial sums (any n) into out[0]: for producers of partials outside this file (the fused
+// forward's per-region partials, raster_forward.hip)
+int launch_l1_finish(const float *partials, int n, float *out, hipStream_t s) {
+  hipLaunchKernelGGL(k_l1_finish, dim3(1), dim3(kFinishThreads), 0, s, partials, n, out);
   return check_launch();
 }
 

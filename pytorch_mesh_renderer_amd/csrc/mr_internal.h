@@ -182,6 +182,15 @@ int launch_render_forward(const float *vertices, const float *transforms, const 
                           int L, float *clip, int32_t *ids, float *bary, float *z, int want_z, float *rgba,
                           uint8_t *rgba_u8, void *corner_records, void *backward_prepared, uint8_t *empty_regions, void *ws,
                           hipStream_t s);
+// ... and mean|rgba - target| (loss, sign codes) out of the same pass; partials: render_forward_l1_partials() floats
+size_t render_forward_l1_partials(int B, int W, int H);
+int launch_render_forward_l1(const float *vertices, const float *transforms, const float *normals,
+                             const float *diffuse, const int32_t *tris, const float *light_pos,
+                             const float *light_col, const float *ambient, int B, int V, int T, int W, int H,
+                             int L, float *clip, int32_t *ids, float *bary, float *z, int want_z, float *rgba,
+                             uint8_t *rgba_u8, void *corner_records, void *backward_prepared, uint8_t *empty_regions, void *ws,
+                             const float *target, const uint8_t *target_empty, float *loss, uint8_t *signs, float *partials,
+                             hipStream_t s);
 // the G-buffer and the specular term's across-pixels norms (norms2 [B,L], L <= 4) in one pass (raster_forward.hip)
 size_t rasterize_specular_norms_ws(int B, int V, int T, int W, int H);
 int launch_rasterize_specular_norms(const float *clip, const int32_t *tris, const float *normals, const float *positions,
@@ -212,6 +221,7 @@ int launch_shade_specular_backward(const float *drgba, const uint8_t *signs, con
 int launch_l1_forward(const float *a, const float *b, size_t n, float *out, uint8_t *signs, float *partials,
                       hipStream_t s);
 int launch_l1_backward(const uint8_t *signs, size_t n, const float *upstream, float *da, hipStream_t s);
+int launch_l1_finish(const float *partials, int n, float *out, hipStream_t s);
 int launch_image_empty_regions(const float *image, int B, int H, int W, uint8_t *map, hipStream_t s);
 int launch_l1_forward_regions(const float *a, const float *b, int B, int H, int W, const uint8_t *empty_a,
                               const uint8_t *empty_b, float *out, uint8_t *signs, float *partials, hipStream_t s);

@@ -45,6 +45,7 @@
 #include <type_traits>
 
 #include "mr_internal.h"
+#include "l1_code.h"
 #include "shade_pixel.h"
 #include "spec_pixel.h"
 
@@ -699,6 +700,13 @@ struct RasterShade {
   // reflection . camera dot product per light, summed per region; shade_spec.hip's norm pass then does not run.
   const float *__restrict__ camera = nullptr;        // [B,3]
   float *__restrict__ norm_partials = nullptr;       // [regions][8]: sums for up to four lights, the covered-pixel count, padding
+  // L1 (with SHADE): mean|rgba - target| against a target the caller has named, as part of the epilogue -- the pixel's
+  // RGBA is still in registers when it is stored, so the loss kernel (and its re-read of the image) does not run.
+  const float *__restrict__ target = nullptr;         // [B,H,W,4], image rows like rgba
+  const uint8_t *__restrict__ target_empty = nullptr; // nullptr, or the target's 64 x 64 block map (mr_image_empty_regions; 64-pixel regions only)
+  uint8_t *__restrict__ l1_signs = nullptr;           // [B*H*W]: a pixel's four 2-bit sign codes, as mr_l1_loss_forward lays them out
+  float *__restrict__ l1_partials = nullptr;          // [n_regions]: sum |d| of the region's pixels times l1_inv_n (closed by k_l1_finish)
+  float l1_inv_n = 0.0f;                              // 1 / (4 B H W)
 };
 
 #ifndef MR_RASTER_STORE_AUX
@@ -745,6 +753,20 @@ struct RasterShade {
 #ifndef MR_RASTER_SHADE_WAVES
 #define MR_RASTER_SHADE_WAVES 6  // measured against 7 (more spills) and 5: 0.336 / 0.352 / 0.347 ms at 1024^2 x 32
 #endif
+#ifndef MR_RASTER_SHADE_L1_WAVES
+#define MR_RASTER_SHADE_L1_WAVES 5   // the L1 instantiation's own bound: at 6 it spills 17-31 registers, and with the prefetch the allocator
+                                     // then breaks store_b96_soffset's protection (tools/check_wide_store_hazard.py reports it)
+#endif
+#ifndef MR_RASTER_L1_PREFETCH
+#define MR_RASTER_L1_PREFETCH 1   // the L1 epilogue's target load: 1 = tile n + 1's pixel requested before tile n's stores issue (whole
+                                  // regions: the load has a whole tile walk to arrive; vmcnt retires in order and the compiler's wait
+                                  // is vmcnt(0), which by then only meets stores issued a tile walk earlier); 0 = requested at the
+                                  // start of the tile's own epilogue and consumed behind the shading arithmetic.  Not with 6 waves:
+                                  // see MR_RASTER_SHADE_L1_WAVES
+#endif
+#ifndef MR_RASTER_L1_TARGET_AUX
+#define MR_RASTER_L1_TARGET_AUX 2    // the target is read once per step and is larger than the Infinity Cache: nontemporal, as loss.hip reads it
+#endif
 #ifndef MR_RASTER_INTERP_STORE_AUX
 #define MR_RASTER_INTERP_STORE_AUX 0   // the interpolated image's stores: per-lane pieces of A floats -- through the caches (merged in L2)
 #endif
@@ -767,8 +789,10 @@ struct RasterShade {
 // crowded (configs[3]: ~170 entries per 64 x 64 region against the 106 record slots the bin's unused top offers): the
 // epilogue then reads its winners' records per lane from LDS there too instead of one winner at a time through the scalar
 // cache.  64 slots = 7 KB more LDS: five workgroups per CU instead of six.  Chosen on the host (launch_k_raster_probe).
-template <int R, int PROBE, bool SHADE, int INTERP = 0, int AX = 0, int XREC = 0, bool NORMS = false>
-__global__ __launch_bounds__(kThreads, SHADE ? (XREC ? MR_RASTER_XREC_WAVES : MR_RASTER_SHADE_WAVES) : NORMS ? MR_RASTER_NORMS_WAVES : INTERP >= 12 ? 4 : INTERP ? MR_RASTER_INTERP_WAVES : MR_RASTER_WAVES) void k_raster(
+// L1 (SHADE only): the epilogue also compares the pixel with RasterShade::target -- see there.  Everything it adds sits
+// under `if constexpr (L1)`: the other instantiations are the code they were.
+template <int R, int PROBE, bool SHADE, int INTERP = 0, int AX = 0, int XREC = 0, bool NORMS = false, bool L1 = false>
+__global__ __launch_bounds__(kThreads, SHADE ? (XREC ? MR_RASTER_XREC_WAVES : L1 ? MR_RASTER_SHADE_L1_WAVES : MR_RASTER_SHADE_WAVES) : NORMS ? MR_RASTER_NORMS_WAVES : INTERP >= 12 ? 4 : INTERP ? MR_RASTER_INTERP_WAVES : MR_RASTER_WAVES) void k_raster(
     const TriRec *__restrict__ recs, const TriBox *__restrict__ bbs,
     const float *__restrict__ pxtab, const float *__restrict__ pytab, int T, int W, int H,
     int regions_x, int regions_per_image, int n_regions, int regions_per_xcd,
@@ -781,6 +805,7 @@ __global__ __launch_bounds__(kThreads, SHADE ? (XREC ? MR_RASTER_XREC_WAVES : MR
   static_assert(R == 64 || R == 32, "region edge");
   static_assert(XREC == 0 || (SHADE && XREC % 4 == 0), "extra record slots: the shading epilogue's");
   static_assert(!SHADE || PROBE == 0, "the shading epilogue has no timing probes");
+  static_assert(!L1 || SHADE, "the loss compares the shaded pixel: the shading epilogue's");
   static_assert(INTERP == 0 || (!SHADE && PROBE == 0 && INTERP % 4 == 0 && INTERP <= 16), "one epilogue at a time");
   static_assert(AX == 0 || (INTERP > 0 && AX <= INTERP && AX > INTERP - 4), "a fixed attribute count belongs to its padded variant");
   static_assert(!NORMS || (INTERP == 8 && AX == 6), "the norm epilogue interpolates normals and positions");
@@ -944,6 +969,36 @@ __global__ __launch_bounds__(kThreads, SHADE ? (XREC ? MR_RASTER_XREC_WAVES : MR
       SHADE ? shade.rgba + 4 * ((ptrdiff_t)img_px + ((ptrdiff_t)H - R - Y0) * W + X0) : nullptr, 0, 0x7fffffff,
       kRsrcWord3);
   const CornerRec *img_corners = SHADE ? shade.corners + (size_t)img * T : nullptr;
+  // L1: the target and the sign codes are image-shaped like rgba and addressed at the same origin, lane and tile offsets
+  // (16 B and 1 B per pixel); l1_acc is this lane's sum of |d| over every pixel it shades in the region.
+  const __amdgpu_buffer_rsrc_t rs_tgt = __builtin_amdgcn_make_buffer_rsrc(
+      L1 ? const_cast<float *>(shade.target) + 4 * ((ptrdiff_t)img_px + ((ptrdiff_t)H - R - Y0) * W + X0) : nullptr, 0, 0x7fffffff,
+      kRsrcWord3);
+  const __amdgpu_buffer_rsrc_t rs_sg = __builtin_amdgcn_make_buffer_rsrc(
+      L1 ? shade.l1_signs + ((ptrdiff_t)img_px + ((ptrdiff_t)H - R - Y0) * W + X0) : nullptr, 0, 0x7fffffff, kRsrcWord3);
+  [[maybe_unused]] float l1_acc = 0.0f;
+  [[maybe_unused]] float *s_l1 = nullptr;
+  if constexpr (L1) {
+    __shared__ float s_l1_waves[kWaves];   // (16 B behind the lights: still inside the same LDS granule)
+    s_l1 = s_l1_waves;
+  }
+  // the region's partial sum: a fixed tree per wavefront, the wavefronts in order -- one plain store per region, so the
+  // loss k_l1_finish closes has the same bits from run to run.  Called by the whole workgroup, once.
+  auto l1_commit = [&]() {
+    if constexpr (L1) {
+      float v = l1_acc;
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
+      if (lane == 0) s_l1[wave] = v;
+      __syncthreads();
+      if (tid == 0) {
+        float t = 0.0f;
+#pragma unroll
+        for (int w = 0; w < kWaves; ++w) t += s_l1[w];
+        shade.l1_partials[region] = t * shade.l1_inv_n;
+      }
+    }
+  };
   const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(
       (INTERP && !NORMS) ? shade.attr_out + region_pix * (size_t)attr_n : nullptr, 0, 0x7fffffff, kRsrcWord3);
   const float *img_attr_records = INTERP ? shade.attr_records + (size_t)img * T * (3 * INTERP) : nullptr;
@@ -1005,6 +1060,34 @@ __global__ __launch_bounds__(kThreads, SHADE ? (XREC ? MR_RASTER_XREC_WAVES : MR
   if (PROBE == 0 && n_cand == 0 && X1 - X0 == R && Y1 - Y0 == R) {  // workgroup-uniform
     constexpr int kRowsPerInst = kWave / R;
     const int x = lane % R;
+    if constexpr (L1) {
+      // The image is transparent black here.  A target block known to be empty too: zero codes, nothing to add.  Else
+      // d = 0 - t from the target's rows, in the row-shaped walk of the stores below (a row of codes is one 64-byte run),
+      // four rows requested at a time and ahead of the region's stores (vmcnt retires in order).
+      typedef float v4f __attribute__((ext_vector_type(4)));
+      const bool tgt_empty = R == 64 && shade.target_empty != nullptr && shade.target_empty[region] != 0;   // workgroup-uniform
+      constexpr int kStep = kWaves * kRowsPerInst, kBatch = 4;
+      static_assert(R % (kStep * kBatch) == 0, "whole batches of rows");
+      for (int y0 = wave * kRowsPerInst + lane / R; y0 < R; y0 += kStep * kBatch) {
+        v4f t[kBatch];
+        if (!tgt_empty) {
+#pragma unroll
+          for (int u = 0; u < kBatch; ++u)
+            t[u] = __builtin_bit_cast(v4f, __builtin_amdgcn_raw_buffer_load_b128(
+                                               rs_tgt, (unsigned)((R - 1 - (y0 + u * kStep)) * W + x) * 16u, 0, MR_RASTER_L1_TARGET_AUX));
+        }
+#pragma unroll
+        for (int u = 0; u < kBatch; ++u) {
+          unsigned code = 0u;
+          if (!tgt_empty) {
+            const float d0 = 0.0f - t[u].x, d1 = 0.0f - t[u].y, d2 = 0.0f - t[u].z, d3 = 0.0f - t[u].w;
+            l1_acc += abs_sum4(d0, d1, d2, d3);
+            code = sign_code4(d0, d1, d2, d3);
+          }
+          __builtin_amdgcn_raw_buffer_store_b8((unsigned char)code, rs_sg, (unsigned)((R - 1 - (y0 + u * kStep)) * W + x), 0, 0);
+        }
+      }
+    }
     for (int y = wave * kRowsPerInst + lane / R; y < R; y += kWaves * kRowsPerInst) {
       const unsigned pix = (unsigned)(y * W + x);
       __builtin_amdgcn_raw_buffer_store_b32(0u, rs_ids, pix * 4u, 0, MR_RASTER_STORE_AUX_IDS);
@@ -1028,6 +1111,7 @@ __global__ __launch_bounds__(kThreads, SHADE ? (XREC ? MR_RASTER_XREC_WAVES : MR
         }
       }
     }
+    l1_commit();
     return;
   }
   // Every wavefront of this kernel is fully populated (256-thread workgroups, padding workgroups
@@ -1077,6 +1161,19 @@ __global__ __launch_bounds__(kThreads, SHADE ? (XREC ? MR_RASTER_XREC_WAVES : MR
     // wavefront w walks tiles w, w + 4, ... (row-major tile numbering).  (Walking pairs of
     // horizontally adjacent tiles back to back, so that both halves of a 128-byte line come from
     // one wavefront, was measured: no difference.)
+    typedef float l1_v4f __attribute__((ext_vector_type(4)));
+    // L1, whole regions: the target pixel of the wavefront's NEXT tile is in flight while this tile is walked (see
+    // MR_RASTER_L1_PREFETCH); ragged regions skip tiles and request theirs inside the tile's own epilogue.
+    constexpr bool l1_prefetch = L1 && MR_RASTER_L1_PREFETCH && full;
+    auto l1_request = [&](const int t) -> l1_v4f {
+      const unsigned lane_rgba = (unsigned)((kTileH - 1 - ly) * W + lx) * 16u;
+      const int tile_rgba = ((R - kTileH - (t / kTilesX) * kTileH) * W + (t % kTilesX) * kTileW) * 16;
+      return __builtin_bit_cast(l1_v4f, __builtin_amdgcn_raw_buffer_load_b128(rs_tgt, lane_rgba, tile_rgba, MR_RASTER_L1_TARGET_AUX));
+    };
+    [[maybe_unused]] l1_v4f tgt_next = {0.0f, 0.0f, 0.0f, 0.0f};
+    if constexpr (l1_prefetch) {
+      if (last_round) tgt_next = l1_request(wave);
+    }
     {
     for (int tile = wave; tile < kTiles; tile += kWaves) {
       const int ty = tile / kTilesX, tx = tile % kTilesX;
@@ -1332,6 +1429,13 @@ __global__ __launch_bounds__(kThreads, SHADE ? (XREC ? MR_RASTER_XREC_WAVES : MR
         // the rule of k_shade_forward: a pixel is shaded iff alpha = clamp(2 sum(bary)) > 0
         const bool live = in_image && ((2.0f * st.b0 + 2.0f * st.b1) + 2.0f * st.b2) > 0.0f;
         float4 rgba = make_float4(0.f, 0.f, 0.f, 0.f);
+        [[maybe_unused]] l1_v4f tgt = {0.0f, 0.0f, 0.0f, 0.0f};
+        if constexpr (l1_prefetch) {
+          tgt = tgt_next;
+          if (tile + kWaves < kTiles) tgt_next = l1_request(tile + kWaves);   // wave-uniform; ahead of this tile's stores
+        } else if constexpr (L1) {
+          if (in_image) tgt = l1_request(tile);
+        }
         // The corner attributes come through the SCALAR cache, one winning triangle of the tile at
         // a time (a 64-pixel tile shows ~3 of them): scalar loads count on lgkmcnt, so their wait
         // leaves the G-buffer stores of the previous tile alone -- vector loads count on vmcnt
@@ -1415,6 +1519,12 @@ __global__ __launch_bounds__(kThreads, SHADE ? (XREC ? MR_RASTER_XREC_WAVES : MR
           const int tile_rgba = ((R - kTileH - ty * kTileH) * W + tx * kTileW) * 16;
           store_b128_soffset<MR_RASTER_STORE_AUX_RGBA>(__builtin_bit_cast(v4u, v4f{rgba.x, rgba.y, rgba.z, rgba.w}), rs_rgba,
                                                        lane_rgba, tile_rgba);
+          if constexpr (L1) {
+            // on the very values just stored; the code byte through the caches (a tile row of codes is a 16-byte run)
+            const float d0 = rgba.x - tgt.x, d1 = rgba.y - tgt.y, d2 = rgba.z - tgt.z, d3 = rgba.w - tgt.w;
+            l1_acc += abs_sum4(d0, d1, d2, d3);
+            __builtin_amdgcn_raw_buffer_store_b8((unsigned char)sign_code4(d0, d1, d2, d3), rs_sg, lane_rgba / 16u, tile_rgba / 16, 0);
+          }
           if (shade.rgba8) {  // workgroup-uniform: the 8-bit frame for the multi-GPU hand-over, 4 B/px
             auto u8 = [](float v) { return (unsigned)(fminf(fmaxf(v, 0.0f), 1.0f) * 255.0f); };  // NaN -> 0
             const unsigned packed = u8(rgba.x) | (u8(rgba.y) << 8) | (u8(rgba.z) << 16) | (u8(rgba.w) << 24);
@@ -1679,6 +1789,7 @@ __global__ __launch_bounds__(kThreads, SHADE ? (XREC ? MR_RASTER_XREC_WAVES : MR
     round_base = next_base;
     if (round_base < n_cand) __syncthreads();  // tiles done with the bin; orders the state stores
   } while (round_base < n_cand);
+  l1_commit();
   if constexpr (NORMS) {   // the region's row of partial sums: fixed tree per wavefront, fixed order over the wavefronts
     __shared__ float s_norm[kWaves][5];
     float v[5] = {norm_acc[0], norm_acc[1], norm_acc[2], norm_acc[3], norm_covered};
@@ -1755,9 +1866,9 @@ struct RasterArgs {
   RasterShade shade;  // rgba == nullptr: G-buffer only
 };
 
-template <int R, int PROBE, bool SHADE = false, int INTERP = 0, int AX = 0, int XREC = 0, bool NORMS = false>
+template <int R, int PROBE, bool SHADE = false, int INTERP = 0, int AX = 0, int XREC = 0, bool NORMS = false, bool L1 = false>
 void launch_k_raster(const RasterArgs &a, dim3 grid, hipStream_t s) {
-  hipLaunchKernelGGL((k_raster<R, PROBE, SHADE, INTERP, AX, XREC, NORMS>), grid, dim3(kThreads), 0, s, a.recs, a.bbs, a.pxtab, a.pytab, a.T,
+  hipLaunchKernelGGL((k_raster<R, PROBE, SHADE, INTERP, AX, XREC, NORMS, L1>), grid, dim3(kThreads), 0, s, a.recs, a.bbs, a.pxtab, a.pytab, a.T,
                      a.W, a.H, a.regions_x, a.per_image, a.n_regions, a.per_xcd, a.cell_ids, a.cell_count,
                      a.cell_split, a.cells_x, a.cells_per_image, a.region_ids, a.region_count, a.order_count,
                      a.order_list, a.ids, a.bary, a.z, a.shade);
@@ -1767,8 +1878,12 @@ template <int R>
 void launch_k_raster_probe(const RasterArgs &a, dim3 grid, hipStream_t s) {
   if (a.shade.rgba) {
     // crowded launches (triangles per 64 x 64 pixels of image): the instantiation with extra record slots, see XREC
-    if (MR_RASTER_XREC > 0 && R == 64 && (double)a.T * 4096.0 >= (double)MR_RASTER_XREC_DENSITY * a.W * a.H)
-      return launch_k_raster<R, 0, true, 0, 0, (R == 64 ? MR_RASTER_XREC : 0)>(a, grid, s);
+    const bool crowded = MR_RASTER_XREC > 0 && R == 64 && (double)a.T * 4096.0 >= (double)MR_RASTER_XREC_DENSITY * a.W * a.H;
+    if (a.shade.l1_partials) {   // the loss against a named target inside the epilogue: the same choice of record slots
+      if (crowded) return launch_k_raster<R, 0, true, 0, 0, (R == 64 ? MR_RASTER_XREC : 0), false, true>(a, grid, s);
+      return launch_k_raster<R, 0, true, 0, 0, 0, false, true>(a, grid, s);
+    }
+    if (crowded) return launch_k_raster<R, 0, true, 0, 0, (R == 64 ? MR_RASTER_XREC : 0)>(a, grid, s);
     return launch_k_raster<R, 0, true>(a, grid, s);
   }
   if (a.shade.norm_partials) return launch_k_raster<R, 0, false, 8, 6, 0, true>(a, grid, s);   // the specular norm as the epilogue
@@ -2024,6 +2139,29 @@ int launch_render_forward(const float *vertices, const float *transforms, const 
                           int L, float *clip, int32_t *ids, float *bary, float *z, int want_z, float *rgba,
                           uint8_t *rgba_u8, void *corner_records, void *backward_prepared, uint8_t *empty_regions, void *ws,
                           hipStream_t s) {
+  return launch_render_forward_l1(vertices, transforms, normals, diffuse, tris, light_pos, light_col, ambient, B, V, T, W, H, L,
+                                  clip, ids, bary, z, want_z, rgba, rgba_u8, corner_records, backward_prepared, empty_regions, ws,
+                                  nullptr, nullptr, nullptr, nullptr, nullptr, s);
+}
+
+// one float per region of the launch (64- or 32-pixel regions, as region_edge chooses)
+size_t render_forward_l1_partials(int B, int W, int H) {
+  const int edge = region_edge(B, W, H);
+  return (size_t)((W + edge - 1) / edge) * ((H + edge - 1) / edge) * B;
+}
+
+// launch_render_forward, and -- with `target` -- mean|rgba - target| with its sign codes out of the same pass: every
+// region leaves one partial sum (RasterShade::l1_partials), k_l1_finish adds them in a fixed order.
+int launch_render_forward_l1(const float *vertices, const float *transforms, const float *normals,
+                             const float *diffuse, const int32_t *tris, const float *light_pos,
+                             const float *light_col, const float *ambient, int B, int V, int T, int W, int H,
+                             int L, float *clip, int32_t *ids, float *bary, float *z, int want_z, float *rgba,
+                             uint8_t *rgba_u8, void *corner_records, void *backward_prepared, uint8_t *empty_regions, void *ws,
+                             const float *target, const uint8_t *target_empty, float *loss, uint8_t *signs, float *partials,
+                             hipStream_t s) {
+  if (target && (size_t)B * W * H == 0) {
+    if (zero_async(loss, sizeof(float), s) != hipSuccess) return check_launch();
+  }
   if ((size_t)B * W * H == 0 || !MR_SETUP_TRANSFORMS)   // (no pixels: the setup kernel does not run; the clip-space vertices are still an output)
   {
     const int rc = launch_vertex_transform(vertices, transforms, B, V, clip, s);
@@ -2043,10 +2181,18 @@ int launch_render_forward(const float *vertices, const float *transforms, const 
     setup.xf = (const float4 *)transforms;
     setup.clip_out = (float4 *)clip;
   }
-  return raster_forward(clip, tris, B, V, T, W, H, ids, bary, z,
-                        RasterShade{corners, Lights{light_pos, light_col, ambient, L}, rgba, (uint32_t *)rgba_u8, want_z, nullptr,
-                                    nullptr, nullptr, 0, region_edge(B, W, H) == 64 ? empty_regions : nullptr},
-                        setup, ws, s);
+  RasterShade shade{corners, Lights{light_pos, light_col, ambient, L}, rgba, (uint32_t *)rgba_u8, want_z, nullptr,
+                    nullptr, nullptr, 0, region_edge(B, W, H) == 64 ? empty_regions : nullptr};
+  if (target) {
+    shade.target = target;
+    shade.target_empty = region_edge(B, W, H) == 64 ? target_empty : nullptr;
+    shade.l1_signs = signs;
+    shade.l1_partials = partials;
+    shade.l1_inv_n = 1.0f / (float)((size_t)B * H * W * 4);
+  }
+  const int rc = raster_forward(clip, tris, B, V, T, W, H, ids, bary, z, shade, setup, ws, s);
+  if (rc != MR_OK || !target) return rc;
+  return launch_l1_finish(partials, (int)render_forward_l1_partials(B, W, H), loss, s);
 }
 
 }  // namespace mr

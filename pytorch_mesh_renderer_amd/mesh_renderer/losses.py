@@ -35,14 +35,22 @@ USE_FUSED_RENDER_LOSS = os.environ.get("MR_FUSED_RENDER_LOSS", "1") != "0"   # F
 
 def remember_target(target):
     """Opt-in for a FIXED loss target (an optimisation loop compares every step's render with the same image): finds
-    which 64 x 64 blocks of `target` are all zeros, once, and keeps that map on the tensor; see l1_loss, TARGET."""
+    which 64 x 64 blocks of `target` are all zeros, once, and keeps that map on the tensor; see l1_loss, TARGET.
+
+    The renderer also learns of the target (one weak reference to the most recently remembered target per device and
+    shape): a differentiable render() of that shape on the fused diffuse path then compares each pixel with the target
+    while it still holds it in registers, and l1_loss(image, target) -- or torch.mean(torch.abs(image - target)) --
+    picks the loss and its sign codes up from there: the loss kernel and its re-read of the image (16 B/px) do not
+    run.  The price: a render() of the same shape made for ANOTHER purpose while the target is remembered pays one
+    extra read of the target (16 B/px); forget_target(target) ends that.  Calling remember_target again on the same
+    tensor (after target.copy_(new)) refreshes the map in place, so a captured step (capture_step) follows it."""
     from .rasterize_triangles_ext import remember_target_map
     remember_target_map(target)
     return target
 
 
 def forget_target(target):
-    """Drops remember_target's map."""
+    """Drops remember_target's map and the renderer's reference to the target."""
     from .rasterize_triangles_ext import forget_target_map
     forget_target_map(target)
 
@@ -77,5 +85,6 @@ def l1_loss(image, target):
                                              record["has_ambient"], record["has_transforms"])
         if record is not None:
             return FusedPhongL1Loss.apply(image, target, *record["inputs"], record["saved"],
-                                          record.get("prepared_state"), record.get("empty_regions"))
+                                          record.get("prepared_state"), record.get("empty_regions"),
+                                          record.get("l1_in_forward"))
     return _MeanAbsError.apply(image, target)

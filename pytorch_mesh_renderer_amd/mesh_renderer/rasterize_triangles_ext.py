@@ -129,9 +129,13 @@ class FusedAttributeRasterizer(torch.autograd.Function):
 #                            mesh_renderer.to_uint8(image) then hands them out instead of converting
 #                            the float image in a pass of its own.  For callers that export every frame
 #                            (the multi-GPU hand-over of bench.py).
-# Defaults come from the environment (MR_SHADING_EPILOGUE, MR_EMIT_UINT8_FRAMES) once, at import.
+#   loss_in_forward(False)   the one-pass forward does NOT compute mean|image - target| for a remembered target
+#                            (losses.remember_target): the loss kernel reads the image back, as it does for any other
+#                            target.  For A/B runs and the parity tests.
+# Defaults come from the environment (MR_SHADING_EPILOGUE, MR_EMIT_UINT8_FRAMES, MR_LOSS_IN_FORWARD) once, at import.
 _DEFAULTS = {"shading_epilogue": os.environ.get("MR_SHADING_EPILOGUE", "1") != "0",
-             "emit_uint8_frames": os.environ.get("MR_EMIT_UINT8_FRAMES", "0") != "0"}
+             "emit_uint8_frames": os.environ.get("MR_EMIT_UINT8_FRAMES", "0") != "0",
+             "loss_in_forward": os.environ.get("MR_LOSS_IN_FORWARD", "1") != "0"}
 _scoped = threading.local()
 
 
@@ -160,6 +164,11 @@ def shading_epilogue(on):
 def emit_uint8_frames(on):
     """with emit_uint8_frames(True): image = render(...); frames = to_uint8(image)."""
     return _scoped_switch("emit_uint8_frames", on)
+
+
+def loss_in_forward(on):
+    """with loss_in_forward(False): image = render(...) -- see the comment above."""
+    return _scoped_switch("loss_in_forward", on)
 
 
 PREPARE_BACKWARD = True   # False: the backward always runs its own setup kernel (A/B, tests)
@@ -195,10 +204,23 @@ class FusedPhongRenderer(torch.autograd.Function):
                        and not _native.deterministic())
         prepared = None
         empty_regions = None
+        # The loss in the forward: the caller has named a fixed target of this image's shape (losses.remember_target) and
+        # will differentiate the image -- the usual step is loss(image, target).backward().  The epilogue then reads
+        # the target next to the pixel it is about to store and leaves mean|image - target| and its sign codes;
+        # FusedPhongL1Loss picks them up if it is handed that very target (and runs the loss kernel for any other).
+        l1_target = l1_map = None
+        ctx.l1_in_forward = None
+        if epilogue and any(needs) and _switch("loss_in_forward"):
+            l1_target, l1_map = _remembered_target(verts.device, (verts.shape[0], int(image_height), int(image_width), 4))
         if epilogue:
             out = _native.render_forward(
                 verts, xf, args[0], args[1], triangles, lp, li, amb, int(image_width), int(image_height),
-                want_z=False, want_u8=bool(want_frames), prepare_backward=prepare, want_empty_regions=EMPTY_REGIONS)
+                want_z=False, want_u8=bool(want_frames), prepare_backward=prepare, want_empty_regions=EMPTY_REGIONS,
+                l1_target=l1_target.detach() if l1_target is not None else None,
+                l1_target_empty=l1_map if EMPTY_REGIONS else None)
+            if l1_target is not None:
+                ctx.l1_in_forward = {"target_key": _target_key(l1_target), "loss": out[-1][0], "signs": out[-1][1]}
+                out = out[:-1]
             clip, ids, bary, _, rgba, corner_records = out[:6]
             if want_frames:
                 frames = out[6]
@@ -284,6 +306,8 @@ def remember_fused_render(node, inputs, image=None, kind="diffuse"):
                             "has_transforms": getattr(node, "has_transforms", None),
                             "prepared_state": getattr(node, "prepared_state", None),
                             "empty_regions": getattr(node, "empty_regions", None),
+                            # {target_key, loss, signs}: the forward compared the image with the remembered target
+                            "l1_in_forward": getattr(node, "l1_in_forward", None),
                             # the empty-block map describes what the renderer WROTE: an in-place edit of the image
                             # (image[..., 3] = 1 under no_grad keeps the grad_fn) bumps this counter and voids it
                             "image_version": image._version if image is not None else None}
@@ -293,8 +317,8 @@ def take_fused_render(image):
     """The record of render()'s node behind `image` (None when `image` is not render()'s own output: a tensor derived
     from it has another node).  The record stays with the node: any number of losses may be built on one image, each
     differentiates straight to the renderer's inputs and the contributions add up.  If the image was edited in place
-    since the renderer wrote it, the record comes back WITHOUT the renderer's empty-block map (the loss then reads
-    every pixel)."""
+    since the renderer wrote it, the record comes back WITHOUT the renderer's empty-block map and without the loss the
+    forward computed on what it wrote (the loss kernel then reads every pixel)."""
     node = image.grad_fn
     if node is None:
         return None
@@ -303,7 +327,7 @@ def take_fused_render(image):
     except TypeError:   # a built-in node (MulBackward0, ...) cannot even be weakly referenced: not ours
         return None
     if record is not None and record.get("image_version") != image._version:
-        record = dict(record, empty_regions=None)
+        record = dict(record, empty_regions=None, l1_in_forward=None)
     return record
 
 
@@ -314,23 +338,58 @@ def take_fused_render(image):
 # pointer, shape and version counter are what they were when it was made; anything else -- another target, an in-place
 # torch write -- means no map, and the loss reads every block.  A write the counter does not see (target.data, DLPack,
 # a raw kernel) after remember_target is the caller's to follow with another remember_target / forget_target.
+#
+# The most recently remembered target of every (device, shape) is also known to the RENDERER, by one weak reference:
+# FusedPhongRenderer.forward compares an image of that shape with it inside its own pass (loss_in_forward).  A map that
+# exists is refreshed IN PLACE by the next remember_target of the same tensor: a captured step (capture_step) has the
+# addresses of the target and of its map baked in, and target.copy_(new); remember_target(target) must reach it.
+_remembered_targets = {}   # (device, shape) -> weakref.ref(target)
+
+
+def _target_key(target):
+    return (target.data_ptr(), target._version, tuple(target.shape))
+
+
 def remember_target_map(target):
     if target.dim() != 4 or target.shape[-1] != 4 or target.dtype != torch.float32 or not target.is_cuda:
         raise ValueError("remember_target expects a [B, H, W, 4] float32 image on the GPU")
-    target._mr_empty_regions = ((target.data_ptr(), target._version, tuple(target.shape)),
-                                _native.image_empty_regions(target.detach()))
+    kept = getattr(target, "_mr_empty_regions", None)
+    same_place = kept is not None and kept[0][0] == target.data_ptr() and kept[0][2] == tuple(target.shape) \
+        and kept[1].device == target.device
+    target._mr_empty_regions = (_target_key(target),
+                                _native.image_empty_regions(target.detach(), out=kept[1] if same_place else None))
+    _remembered_targets[(target.device, tuple(target.shape))] = weakref.ref(target)
 
 
 def forget_target_map(target):
     if hasattr(target, "_mr_empty_regions"):
         del target._mr_empty_regions
+    where = (target.device, tuple(target.shape))
+    ref = _remembered_targets.get(where)
+    if ref is not None and (ref() is None or ref() is target):
+        del _remembered_targets[where]
 
 
 def _target_empty_regions(target):
     kept = getattr(target, "_mr_empty_regions", None)
-    if kept is not None and kept[0] == (target.data_ptr(), target._version, tuple(target.shape)):
+    if kept is not None and kept[0] == _target_key(target):
         return kept[1]
     return None
+
+
+def _remembered_target(device, shape):
+    """(target, its empty-block map) for the live remembered target of that device and shape whose key still holds --
+    not edited in place, not moved -- else (None, None)."""
+    ref = _remembered_targets.get((device, tuple(shape)))
+    target = ref() if ref is not None else None
+    if target is None:
+        if ref is not None:
+            del _remembered_targets[(device, tuple(shape))]
+        return None, None
+    empty = _target_empty_regions(target)
+    if empty is None or not target.is_contiguous():
+        return None, None
+    return target, empty
 
 
 class FusedPhongL1Loss(torch.autograd.Function):
@@ -348,12 +407,21 @@ class FusedPhongL1Loss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, image, target, vertices, transforms, normals, diffuse, light_positions,
-                light_intensities, ambient, render_saved, prepared_state=None, empty_regions=None):
-        # the renderer knows which 64 x 64 blocks of its image are empty; the target's are known if the caller named it
-        # (losses.remember_target): blocks empty on both sides are not read
-        empty_target = _target_empty_regions(target) if empty_regions is not None else None
-        loss, signs = _native.l1_loss_forward(image.detach(), target.detach(), want_signs=True,
-                                              empty_a=empty_regions, empty_b=empty_target)
+                light_intensities, ambient, render_saved, prepared_state=None, empty_regions=None, l1_in_forward=None):
+        # l1_in_forward (take_fused_render hands it over only for an image nobody edited): the renderer's forward already
+        # compared the image with the target it knew of.  If that is THIS target, unchanged since, the loss and the sign
+        # codes are taken from there and no kernel runs; any other target is compared here, as ever.
+        ctx.loss_from_forward = l1_in_forward is not None and l1_in_forward["target_key"] == _target_key(target)
+        if ctx.loss_from_forward:
+            # (detach(): a new tensor object on the same scalar -- several losses may be built on one image)
+            loss, signs = l1_in_forward["loss"].detach(), l1_in_forward["signs"]
+            _native.close_pending_timer(_native.TIMER_L1_FORWARD, image.device)
+        else:
+            # the renderer knows which 64 x 64 blocks of its image are empty; the target's are known if the caller named it
+            # (losses.remember_target): blocks empty on both sides are not read
+            empty_target = _target_empty_regions(target) if empty_regions is not None else None
+            loss, signs = _native.l1_loss_forward(image.detach(), target.detach(), want_signs=True,
+                                                  empty_a=empty_regions, empty_b=empty_target)
         ctx.image_shape = image.shape
         ctx.prepared_state = prepared_state
         ctx.empty_regions = empty_regions
@@ -382,14 +450,14 @@ class FusedPhongL1Loss(torch.autograd.Function):
             dimage = _native.l1_loss_backward(signs, ctx.image_shape, upstream)
             if ctx.needs_input_grad[1]:
                 dtarget = -dimage
-            return (dimage, dtarget) + (None,) * 10
+            return (dimage, dtarget) + (None,) * 11
         dverts, dxf, dn, dd, _, dlp, dli, damb = FusedPhongRenderer._input_grads(
             ctx.saved_tensors[2:], ctx.needs_input_grad[3], any(ctx.needs_input_grad[6:9]), upstream,
             l1_signs=signs, needs_normal_grad=ctx.needs_input_grad[4], needs_diffuse_grad=ctx.needs_input_grad[5],
             prepared_state=ctx.prepared_state, empty_regions=ctx.empty_regions)
         if ctx.needs_input_grad[1]:
             dtarget = -_native.l1_loss_backward(signs, ctx.image_shape, upstream)
-        return None, dtarget, dverts, dxf, dn, dd, dlp, dli, damb, None, None, None
+        return None, dtarget, dverts, dxf, dn, dd, dlp, dli, damb, None, None, None, None
 
 
 # False (or MR_FUSE_SPECULAR_NORMS=0 at import): the specular renderer rasterizes with mr_rasterize_forward and runs the
