@@ -506,6 +506,47 @@ int mr_l1_loss_forward(const float *a, const float *b, size_t n, float *loss, ui
 int mr_l1_loss_backward(const uint8_t *signs, size_t n, const float *upstream, float *da,
                         void *stream);
 
+/* ---- structural-similarity image loss (no reference counterpart) ----------------------------
+ * The mean SSIM (Wang et al. 2004) of two images ("Image losses: SSIM"), one stencil pass each way.
+ * Channels are independent.  Window g[i] ~ exp(-(i - r)^2 / (2 sigma^2)), i = 0 .. window - 1, r = (window - 1) / 2,
+ * normalised to sum 1 in double and rounded to float on the host inside the library; G = g x g.  Per channel and pixel
+ *   mx = G*x  my = G*y  sxx = G*(x x) - mx^2  syy = G*(y y) - my^2  sxy = G*(x y) - mx my
+ *   map = ((2 mx my + c1)(2 sxy + c2)) / ((mx^2 + my^2 + c1)(sxx + syy + c2))
+ * MR_SSIM_SAME: taps outside the image contribute zero, the weights are not renormalised, the map is [B,H,W,C]
+ * (conv2d with padding window / 2); MR_SSIM_VALID: only windows wholly inside, the map is
+ * [B,H-window+1,W-window+1,C] and H, W >= window.  The value is the plain mean of the map.
+ *   image, target [B,H,W,C] f32, 1 <= C <= 4; every pointer 16-byte aligned when C = 4
+ *   window        odd, 3 .. 11;  sigma > 0;  c1, c2 > 0: (k1 L)^2 and (k2 L)^2 (with 0 the map would be 0 / 0 where
+ *                 both images are flat)
+ *   grads         mask of MR_SSIM_GRAD_*: which input the backward will differentiate
+ *   mean          1 float out (device)
+ *   map           the map out, or NULL (not written)
+ *   saved         mr_ssim_saved_floats() floats out, needed unless grads is 0: planes of the map's shape that the
+ *                 backward convolves, each already times 1 / n -- with the map f as a function of the raw moments
+ *                 (mx, my, Exx, Eyy, Exy): d f / d Exx (= d f / d Eyy), d f / d Exy, then d f / d mx if the image is
+ *                 in grads, then d f / d my if the target is
+ *   partials      scratch, mr_ssim_partials() floats: one partial sum per workgroup (a 32 x 16 tile of the map), added
+ *                 in a fixed order by a second launch -- the value is bit-identical from run to run
+ * Backward: upstream (1 float, d L / d mean, read on the device) -> dimage and / or dtarget [B,H,W,C], either may be
+ * NULL (not computed), each only if the forward's grads named it (same grads in both calls):
+ *   d L / d x(q) = upstream ((G*A)(q) + 2 x(q) (G*B)(q) + y(q) (G*C)(q))
+ * with A, B, C the planes d f / d mx, d f / d Exx, d f / d Exy (zero outside the map).  A gather with no atomics:
+ * bit-reproducible in either deterministic mode.  Both calls are asynchronous on `stream`, allocate nothing and do
+ * not synchronise.  1 <= B <= 65535, H, W <= 65535, B H W < 2^36; anything else is MR_EINVAL before any device
+ * call, and the size queries return 0. */
+#define MR_SSIM_SAME 0
+#define MR_SSIM_VALID 1
+#define MR_SSIM_GRAD_IMAGE 1
+#define MR_SSIM_GRAD_TARGET 2
+size_t mr_ssim_partials(int B, int H, int W, int window, int padding);
+size_t mr_ssim_saved_floats(int B, int H, int W, int C, int window, int padding, int grads);
+int mr_ssim_forward(const float *image, const float *target, int B, int H, int W, int C, int window, float sigma,
+                    float c1, float c2, int padding, int grads, float *mean, float *map, float *saved, float *partials,
+                    void *stream);
+int mr_ssim_backward(const float *image, const float *target, const float *saved, const float *upstream, int B, int H,
+                     int W, int C, int window, float sigma, int padding, int grads, float *dimage, float *dtarget,
+                     void *stream);
+
 /* ---- 8-bit frame export ---------------------------------------------------------------
  * The conversion the reference's examples apply on the host before writing PNG / GIF frames,
  * (image * 255.0).astype(np.uint8) (src/examples/example1.py:52, example5.py:81), on the device:
@@ -736,7 +777,7 @@ int mr_tone_map(const float *image, int B, size_t elements_per_image, float gamm
  * number.  mr_soft_backward is covered as well (fixed-point integer atomics into 64-bit copies of its
  * four vertex outputs, scaled for the 1 / sigma and 1 / gamma its contributions carry; its light
  * gradients are fixed-order sums in either mode).  mr_antialias_backward is covered (fixed-point integer atomics for dclip, scaled from a first pass that finds
- * its largest per-vertex contribution).  mr_sh_shade_backward has no atomics and is bit-reproducible in either mode, and so are mr_mesh_regularizer_forward / _backward.  mr_texture_backward is covered (fixed-point integer adds, in LDS and in the workspace, for dtex, scaled from a first pass that finds the largest upstream gradient and from the number of pixels that sample one texture; duv is per pixel in either mode), and so is mr_texture_mip_backward (the same fixed-point scatter into every level of the gradient pyramid, the same scale rule -- a contribution is level weight x tap weight x dout, at most |dout| -- then one gathered pass that converts each level's sums and folds them in a fixed order).  mr_texture_mip_forward and mr_attribute_derivatives have no atomics.  Not covered, float atomics remain: the composed
+ * its largest per-vertex contribution).  mr_sh_shade_backward has no atomics and is bit-reproducible in either mode, and so are mr_mesh_regularizer_forward / _backward and mr_ssim_forward / _backward.  mr_texture_backward is covered (fixed-point integer adds, in LDS and in the workspace, for dtex, scaled from a first pass that finds the largest upstream gradient and from the number of pixels that sample one texture; duv is per pixel in either mode), and so is mr_texture_mip_backward (the same fixed-point scatter into every level of the gradient pyramid, the same scale rule -- a contribution is level weight x tap weight x dout, at most |dout| -- then one gathered pass that converts each level's sums and folds them in a fixed order).  mr_texture_mip_forward and mr_attribute_derivatives have no atomics.  Not covered, float atomics remain: the composed
  * interpolation backward (mr_interpolate_backward, the path for more than 16 attributes).  mr_l1_loss_forward is always deterministic.  Returns the previous setting. */
 int mr_set_deterministic(int on);
 

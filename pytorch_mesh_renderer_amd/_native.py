@@ -320,6 +320,18 @@ def lib():
         except AttributeError as e:   # the regulariser entry points came without an ABI version bump
             raise NativeLibraryError("%s lacks the mesh regulariser entry points (%s): rebuild it (make -C "
                                      "pytorch_mesh_renderer_amd/csrc)" % (LIB_PATH, e))
+        try:
+            L.mr_ssim_partials.argtypes = [ci] * 5
+            L.mr_ssim_partials.restype = sz
+            L.mr_ssim_saved_floats.argtypes = [ci] * 7
+            L.mr_ssim_saved_floats.restype = sz
+            L.mr_ssim_forward.argtypes = [vp, vp] + [ci] * 5 + [cf] * 3 + [ci, ci] + [vp] * 5
+            L.mr_ssim_forward.restype = ci
+            L.mr_ssim_backward.argtypes = [vp] * 4 + [ci] * 5 + [cf, ci, ci, vp, vp, vp]
+            L.mr_ssim_backward.restype = ci
+        except AttributeError as e:   # the SSIM entry points came without an ABI version bump
+            raise NativeLibraryError("%s lacks the SSIM entry points (%s): rebuild it (make -C "
+                                     "pytorch_mesh_renderer_amd/csrc)" % (LIB_PATH, e))
         _lib = L
     return _lib
 
@@ -1792,6 +1804,89 @@ def l1_loss_backward(signs, shape, upstream):
                                        _stream(dev))
     _check(rc, "mr_l1_loss_backward")
     return da
+
+
+SSIM_SAME, SSIM_VALID = 0, 1                # mesh_raster.h, MR_SSIM_*
+SSIM_GRAD_IMAGE, SSIM_GRAD_TARGET = 1, 2
+_SSIM_PADDING = {"same": SSIM_SAME, "valid": SSIM_VALID}
+
+
+def _chk_ssim(image, target, window_size, sigma, padding):
+    """The argument rules of mr_ssim_forward / _backward -> (B, H, W, C, padding code)."""
+    if not torch.is_tensor(image) or not torch.is_tensor(target):
+        raise TypeError("image and target must be tensors")
+    if image.shape != target.shape:
+        raise ValueError("image and target must have the same shape")
+    if image.dim() != 4:
+        raise ValueError("ssim expects [B, H, W, C] images, got shape %s" % (list(image.shape),))
+    if image.dtype != _F32 or target.dtype != _F32:
+        raise RuntimeError("ssim expects float32 tensors")
+    B, H, W, C = image.shape
+    if not 1 <= C <= 4:
+        raise ValueError("ssim supports 1..4 channels, got %d" % C)
+    if B < 1 or H < 1 or W < 1:
+        raise ValueError("ssim needs at least one image of at least one pixel, got shape %s" % (list(image.shape),))
+    if isinstance(window_size, bool) or not isinstance(window_size, int) or window_size % 2 == 0 or \
+            not 3 <= window_size <= 11:
+        raise ValueError("window_size must be an odd integer in [3, 11], got %r" % (window_size,))
+    if not (float(sigma) > 0.0 and float(sigma) < float("inf")):
+        raise ValueError("sigma must be positive and finite, got %r" % (sigma,))
+    if padding not in _SSIM_PADDING:
+        raise ValueError("padding must be 'same' or 'valid', got %r" % (padding,))
+    if padding == "valid" and (H < window_size or W < window_size):
+        raise ValueError("padding='valid' needs H, W >= window_size, got %d x %d for a window of %d"
+                         % (H, W, window_size))
+    return B, H, W, C, _SSIM_PADDING[padding]
+
+
+def ssim_forward(image, target, window_size=11, sigma=1.5, padding="same", c1=1e-4, c2=9e-4, grads=0,
+                 want_map=False):
+    """Mean SSIM of two [B,H,W,C] float32 device images (mr_ssim_forward) -> (0-D tensor, map or None, saved or None).
+
+    grads: mask of SSIM_GRAD_IMAGE | SSIM_GRAD_TARGET, the inputs ssim_backward will differentiate; `saved` is the
+    block of derivative planes it needs (None for grads = 0).  want_map: also the [B,H',W',C] SSIM map."""
+    B, H, W, C, pad = _chk_ssim(image, target, window_size, sigma, padding)
+    if not (c1 > 0.0 and c2 > 0.0 and c1 < float("inf") and c2 < float("inf")):
+        raise ValueError("c1 and c2 must be positive and finite, got %r, %r" % (c1, c2))
+    if grads not in (0, 1, 2, 3):
+        raise ValueError("grads must be a mask of SSIM_GRAD_IMAGE | SSIM_GRAD_TARGET, got %r" % (grads,))
+    dev = _require_device(image, target)
+    L = lib()
+    image, target = image.contiguous(), target.contiguous()
+    Hm, Wm = (H - window_size + 1, W - window_size + 1) if pad == SSIM_VALID else (H, W)
+    out = torch.empty((), dtype=_F32, device=dev)
+    ssim_map = torch.empty(B, Hm, Wm, C, dtype=_F32, device=dev) if want_map else None
+    saved = torch.empty(L.mr_ssim_saved_floats(B, H, W, C, window_size, pad, grads), dtype=_F32, device=dev) \
+        if grads else None
+    partials = torch.empty(L.mr_ssim_partials(B, H, W, window_size, pad), dtype=_F32, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.mr_ssim_forward(_ptr(image), _ptr(target), B, H, W, C, window_size, float(sigma), float(c1), float(c2),
+                               pad, grads, _ptr(out), _ptr(ssim_map), _ptr(saved), _ptr(partials), _stream(dev))
+    _check(rc, "mr_ssim_forward")
+    return out, ssim_map, saved
+
+
+def ssim_backward(image, target, saved, upstream, window_size=11, sigma=1.5, padding="same", grads=SSIM_GRAD_IMAGE,
+                  want_image=True, want_target=False):
+    """(d image, d target) of upstream * mean SSIM from ssim_forward's saved block (same window, padding and grads);
+    a gradient that is not wanted is None and is not computed."""
+    B, H, W, C, pad = _chk_ssim(image, target, window_size, sigma, padding)
+    if grads not in (1, 2, 3):
+        raise ValueError("grads must be a non-empty mask of SSIM_GRAD_IMAGE | SSIM_GRAD_TARGET, got %r" % (grads,))
+    if (want_image and not grads & SSIM_GRAD_IMAGE) or (want_target and not grads & SSIM_GRAD_TARGET):
+        raise ValueError("the forward call saved nothing for a gradient that is wanted now (grads = %d)" % grads)
+    L = lib()
+    _chk("saved", saved, _F32, L.mr_ssim_saved_floats(B, H, W, C, window_size, pad, grads))
+    _chk("upstream gradient of the ssim value", upstream, _F32, 1)
+    dev = _require_device(image, target, saved, upstream)
+    image, target, saved = image.contiguous(), target.contiguous(), saved.contiguous()
+    da = torch.empty(B, H, W, C, dtype=_F32, device=dev) if want_image else None
+    db = torch.empty(B, H, W, C, dtype=_F32, device=dev) if want_target else None
+    with torch.cuda.device(dev):
+        rc = L.mr_ssim_backward(_ptr(image), _ptr(target), _ptr(saved), _ptr(upstream.contiguous()), B, H, W, C,
+                                window_size, float(sigma), pad, grads, _ptr(da), _ptr(db), _stream(dev))
+    _check(rc, "mr_ssim_backward")
+    return da, db
 
 
 def export_u8(image):

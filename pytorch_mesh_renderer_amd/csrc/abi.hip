@@ -1,6 +1,8 @@
 // extern "C" surface of libmesh_raster_hip.so (see include/mesh_raster.h).
 // Argument validation lives here; kernels and launch geometry live in the
 // per-stage .hip files.  No allocation, no synchronisation, no exceptions.
+#include <float.h>
+
 #include "mr_internal.h"
 #include "mesh_raster_debug.h"
 
@@ -788,6 +790,56 @@ inline bool bad_texture_dims(int tex_batched, int Ht, int Wt, int C, int B, int 
 inline bool bad_boundary(int boundary) { return boundary != MR_TEXTURE_WRAP && boundary != MR_TEXTURE_CLAMP; }
 
 inline bool misaligned(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) != 0; }
+
+inline bool bad_ssim_dims(int B, int H, int W, int C, int window, int padding) {
+  if (B < 1 || B > 65535 || H < 1 || W < 1 || H > 65535 || W > 65535 || C < 1 || C > 4) return true;
+  if (window < 3 || window > 11 || window % 2 == 0) return true;
+  if (padding != MR_SSIM_SAME && padding != MR_SSIM_VALID) return true;
+  if (padding == MR_SSIM_VALID && (H < window || W < window)) return true;
+  return (size_t)B * H * W >= ((size_t)1 << 36);   // (16 x 32 tiles: their number stays far below 2^31)
+}
+
+inline bool bad_ssim_grads(int grads) { return grads < 0 || grads > (MR_SSIM_GRAD_IMAGE | MR_SSIM_GRAD_TARGET); }
+
+size_t mr_ssim_partials(int B, int H, int W, int window, int padding) {
+  if (bad_ssim_dims(B, H, W, 1, window, padding)) return 0;
+  return mr::ssim_partials(B, H, W, window, padding);
+}
+
+size_t mr_ssim_saved_floats(int B, int H, int W, int C, int window, int padding, int grads) {
+  if (bad_ssim_dims(B, H, W, C, window, padding) || bad_ssim_grads(grads) || grads == 0) return 0;
+  return (size_t)(grads == (MR_SSIM_GRAD_IMAGE | MR_SSIM_GRAD_TARGET) ? 4 : 3) *
+         mr::ssim_plane_floats(B, H, W, C, window, padding);
+}
+
+int mr_ssim_forward(const float *image, const float *target, int B, int H, int W, int C, int window, float sigma,
+                    float c1, float c2, int padding, int grads, float *mean, float *map, float *saved, float *partials,
+                    void *stream) {
+  if (bad_ssim_dims(B, H, W, C, window, padding) || bad_ssim_grads(grads)) return MR_EINVAL;
+  if (!(sigma > 0.0f) || !(sigma <= FLT_MAX) || !(c1 > 0.0f) || !(c2 > 0.0f) || !(c1 <= FLT_MAX) || !(c2 <= FLT_MAX))
+    return MR_EINVAL;
+  if (!image || !target || !mean || !partials || (grads != 0 && !saved)) return MR_EINVAL;
+  if (C == 4 && (misaligned(image, 16) || misaligned(target, 16) || misaligned(map, 16) || misaligned(saved, 16)))
+    return MR_EINVAL;
+  return mr::launch_ssim_forward(image, target, B, H, W, C, window, sigma, c1, c2, padding, grads, mean, map,
+                                 grads != 0 ? saved : nullptr, partials, (hipStream_t)stream);
+}
+
+int mr_ssim_backward(const float *image, const float *target, const float *saved, const float *upstream, int B, int H,
+                     int W, int C, int window, float sigma, int padding, int grads, float *dimage, float *dtarget,
+                     void *stream) {
+  if (bad_ssim_dims(B, H, W, C, window, padding) || bad_ssim_grads(grads) || grads == 0) return MR_EINVAL;
+  if (!(sigma > 0.0f) || !(sigma <= FLT_MAX)) return MR_EINVAL;
+  if (!image || !target || !saved || !upstream) return MR_EINVAL;
+  // a gradient can only be asked of the planes the forward saved for it
+  if ((dimage && !(grads & MR_SSIM_GRAD_IMAGE)) || (dtarget && !(grads & MR_SSIM_GRAD_TARGET))) return MR_EINVAL;
+  if (dimage == nullptr && dtarget == nullptr) return MR_OK;
+  if (C == 4 && (misaligned(image, 16) || misaligned(target, 16) || misaligned(saved, 16) || misaligned(dimage, 16) ||
+                 misaligned(dtarget, 16)))
+    return MR_EINVAL;
+  return mr::launch_ssim_backward(image, target, saved, upstream, B, H, W, C, window, sigma, padding, grads, dimage,
+                                  dtarget, (hipStream_t)stream);
+}
 
 int mr_texture_forward(const float *tex, const float *uv, const float *mask, int tex_batched, int Ht, int Wt, int C,
                        int B, int W, int H, int boundary, float *out, void *stream) {

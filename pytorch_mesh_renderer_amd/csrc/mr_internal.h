@@ -286,6 +286,14 @@ int launch_texture_mip_backward(const float *dout, const float *tex, const float
 int launch_attribute_derivatives(const int32_t *ids, const float *bary, const float *clip, const int32_t *tris,
                                  const float *attrs, const int32_t *attr_tris, int B, int V, int T, int Va, int W,
                                  int H, int A, float *out, hipStream_t s);
+// SSIM image loss (ssim.hip)
+size_t ssim_partials(int B, int H, int W, int window, int padding);
+size_t ssim_plane_floats(int B, int H, int W, int C, int window, int padding);
+int launch_ssim_forward(const float *a, const float *b, int B, int H, int W, int C, int window, float sigma, float c1,
+                        float c2, int padding, int grads, float *mean, float *map, float *saved, float *partials,
+                        hipStream_t s);
+int launch_ssim_backward(const float *a, const float *b, const float *saved, const float *upstream, int B, int H, int W,
+                         int C, int window, float sigma, int padding, int grads, float *da, float *db, hipStream_t s);
 int soft_max_lights();
 int launch_debug_soft_nearest(const float *p, const float *a, const float *b, int n, float *out, hipStream_t s);
 size_t soft_ws(int B, int V, int T, int W, int H);

@@ -5,7 +5,12 @@ The reference has no loss module; its tests and examples spell the loss out as
 src/examples/example5.py:70-92).  In eager torch that is five passes over the image; this is
 the same quantity as one HIP pass forward (which also packs sign(image - target), 2 bits per
 element) and one backward that reads only those signs.
+
+ssim / photometric_loss: the structural-similarity loss (Wang et al. 2004) and its usual mix with L1, one HIP
+stencil pass forward and one backward (csrc/ssim.hip) instead of five grouped convolutions and their autograd chain.
 """
+import ctypes
+
 import torch
 
 from .. import _native
@@ -88,3 +93,74 @@ def l1_loss(image, target):
                                           record.get("prepared_state"), record.get("empty_regions"),
                                           record.get("l1_in_forward"))
     return _MeanAbsError.apply(image, target)
+
+
+class _MeanSSIM(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, image, target, window_size, sigma, padding, c1, c2):
+        grads = (_native.SSIM_GRAD_IMAGE if ctx.needs_input_grad[0] else 0) | \
+                (_native.SSIM_GRAD_TARGET if ctx.needs_input_grad[1] else 0)
+        image, target = image.detach(), target.detach()
+        value, _, saved = _native.ssim_forward(image, target, window_size, sigma, padding, c1, c2, grads=grads)
+        if grads:
+            ctx.save_for_backward(image, target, saved)
+        ctx.config = (window_size, sigma, padding, grads)
+        return value
+
+    @staticmethod
+    def backward(ctx, grad):
+        image, target, saved = ctx.saved_tensors
+        window_size, sigma, padding, grads = ctx.config
+        da, db = _native.ssim_backward(image, target, saved, grad.to(torch.float32).reshape(1), window_size, sigma,
+                                       padding, grads, want_image=ctx.needs_input_grad[0],
+                                       want_target=ctx.needs_input_grad[1])
+        return da, db, None, None, None, None, None
+
+
+def _ssim_arguments(image, target, window_size=11, sigma=1.5, padding="same", k1=0.01, k2=0.03, data_range=1.0):
+    """Checks everything ssim() takes, before anything is launched -> (window_size, sigma, padding, C1, C2)."""
+    _native._chk_ssim(image, target, window_size, sigma, padding)
+    for name, v in (("k1", k1), ("k2", k2), ("data_range", data_range)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not (0.0 < float(v) < float("inf")):
+            # (C1 = 0 or C2 = 0 makes the map 0 / 0 wherever both images are flat, e.g. a render's empty background)
+            raise ValueError("%s must be a positive finite number, got %r" % (name, v))
+    c1, c2 = (ctypes.c_float((float(k) * float(data_range)) ** 2).value for k in (k1, k2))   # as the kernels get them
+    if not (0.0 < c1 < float("inf") and 0.0 < c2 < float("inf")):
+        raise ValueError("(k1 data_range)^2 and (k2 data_range)^2 must be positive float32 numbers, got %r, %r" % (c1, c2))
+    return window_size, float(sigma), padding, c1, c2
+
+
+def ssim(image, target, window_size=11, sigma=1.5, padding="same", k1=0.01, k2=0.03, data_range=1.0):
+    """Mean structural similarity of two [B, H, W, C] float32 images (1 <= C <= 4, channels independent) as a 0-D
+    tensor, differentiable in both.  Per channel and pixel, with G the window_size x window_size Gaussian of `sigma`
+    (normalised to sum 1):
+
+        mx = G*x   my = G*y   sxx = G*(x x) - mx^2   syy = G*(y y) - my^2   sxy = G*(x y) - mx my
+        ((2 mx my + C1)(2 sxy + C2)) / ((mx^2 + my^2 + C1)(sxx + syy + C2)),   C1 = (k1 data_range)^2, C2 likewise
+
+    padding="same": taps outside the image contribute zero (conv2d(padding=window_size // 2)) and the map is H x W;
+    "valid": only windows wholly inside, H, W >= window_size.  The value is the plain mean of the map.  k1, k2 and
+    data_range must be positive.  A gradient that is not required is not computed, and under no_grad nothing is
+    saved for one; both gradients are gathers without atomics and bit-reproducible."""
+    arguments = _ssim_arguments(image, target, window_size, sigma, padding, k1, k2, data_range)
+    if not torch.is_grad_enabled():   # (needs_input_grad does not look at the grad mode)
+        return _native.ssim_forward(image.detach(), target.detach(), *arguments, grads=0)[0]
+    return _MeanSSIM.apply(image.contiguous(), target.contiguous(), *arguments)
+
+
+def photometric_loss(image, target, ssim_weight=0.2, **ssim_arguments):
+    """(1 - w) l1_loss(image, target) + w (1 - ssim(image, target, **ssim_arguments)), w = ssim_weight in [0, 1].
+
+    The L1 part is l1_loss itself: on render()'s own output it keeps the fused route (sign codes straight into the
+    shading backward), and the SSIM part's dense gradient reaches the renderer through the image's node; the two
+    contributions add up there.  Every argument is checked whatever the weight; a part whose weight is zero is not
+    computed."""
+    if isinstance(ssim_weight, bool) or not isinstance(ssim_weight, (int, float)) or not 0.0 <= ssim_weight <= 1.0:
+        raise ValueError("ssim_weight must be a number in [0, 1], got %r" % (ssim_weight,))
+    _ssim_arguments(image, target, **ssim_arguments)   # (an unknown keyword is a TypeError here, at any weight)
+    w = float(ssim_weight)
+    if w == 0.0:
+        return l1_loss(image, target)
+    if w == 1.0:
+        return 1.0 - ssim(image, target, **ssim_arguments)
+    return (1.0 - w) * l1_loss(image, target) + w * (1.0 - ssim(image, target, **ssim_arguments))
