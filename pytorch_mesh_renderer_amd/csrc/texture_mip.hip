@@ -13,10 +13,11 @@
 //   k_mip_build         one lane per texel of level l + 1, one launch per level (each reads the one before).
 //   k_tex_mip_forward   one lane per pixel, grid (runs, B), like k_tex_forward.
 //   k_tex_mip_backward  k_tex_backward's 64 x 16 tile.  d uv per pixel in gather form.  d tex is scattered into a
-//                       gradient pyramid, ONE WINDOW PASS PER LEVEL PRESENT IN THE TILE: for each level the tile's
-//                       tap box at that level, LDS accumulation when box x C fits the window, the leader-round /
-//                       per-lane atomic fallback otherwise.  The window is 60 KiB here (a tile's box at its own l0
-//                       is up to ~130 x 34 texels: 13k floats at C = 3), two workgroups per CU.
+//                       gradient pyramid, ONE PASS PER LEVEL PRESENT IN THE TILE: for each level one call of
+//                       texture_taps.h's scatter_level (k_tex_backward's pass) with the level's extents, its
+//                       pixels' samples located at that level and dout times the level weight.  The window is
+//                       60 KiB here (a tile's box at its own l0 is up to ~130 x 34 texels: 13k floats at C = 3),
+//                       two workgroups per CU.
 //   k_mip_fold          one lane per level-0 texel: Horner from the coarsest level down, v = g_l + 0.25f v, which is
 //                       dlevel_l[i,j] += 0.25f dlevel_{l+1}[i/2,j/2] applied coarsest first, gathered, no atomics;
 //                       in deterministic mode it reads the fixed-point sums and converts them on the way.
@@ -67,41 +68,26 @@ __device__ __forceinline__ void level_of_detail(float4 da, int Wt, int Ht, int L
   f = lod - fl;
 }
 
-// the bilinear rule of k_tex_forward at one level
+// the bilinear rule (texture_taps.h) at one level
 template <int C, int BOUND>
-__device__ __forceinline__ void bilinear(const float *__restrict__ lvl, float2 q, int Wl, int Hl, float (&o)[C]) {
+__device__ __forceinline__ void level_value(const float *__restrict__ lvl, float2 q, int Wl, int Hl, float (&o)[C]) {
   Sample s;
-  if (!locate(q, Wl, Hl, s)) {  // cannot happen below a level 0 that passed: |x| shrinks with the level
+  if (locate(q, Wl, Hl, s)) {
+    bilinear<C, BOUND>(lvl, s, Wl, Hl, o);
+  } else {  // cannot happen below a level 0 that passed: |x| shrinks with the level
 #pragma unroll
     for (int c = 0; c < C; ++c) o[c] = 0.0f;
-    return;
   }
-  Taps<C, BOUND> t;
-  t.load(lvl, s, Wl, Hl);
-  const float gx = 1.0f - s.fx, gy = 1.0f - s.fy;
-  const float w00 = gx * gy, w01 = s.fx * gy, w10 = gx * s.fy, w11 = s.fx * s.fy;
-#pragma unroll
-  for (int c = 0; c < C; ++c) o[c] = ((w00 * t.t00[c] + w01 * t.t01[c]) + w10 * t.t10[c]) + w11 * t.t11[c];
 }
 
-// d value / d (u, v) of the bilinear rule at one level, contracted with g
+// its d value / d (u, v), contracted with g
 template <int C, int BOUND>
-__device__ __forceinline__ void bilinear_duv(const float *__restrict__ lvl, float2 q, int Wl, int Hl,
-                                             const float (&g)[C], float &du, float &dv) {
+__device__ __forceinline__ void level_duv(const float *__restrict__ lvl, float2 q, int Wl, int Hl, const float (&g)[C],
+                                          float &du, float &dv) {
   du = 0.0f;
   dv = 0.0f;
   Sample s;
-  if (!locate(q, Wl, Hl, s)) return;
-  Taps<C, BOUND> t;
-  t.load(lvl, s, Wl, Hl);
-  const float gx = 1.0f - s.fx, gy = 1.0f - s.fy;
-#pragma unroll
-  for (int c = 0; c < C; ++c) {
-    du += g[c] * (gy * (t.t01[c] - t.t00[c]) + s.fy * (t.t11[c] - t.t10[c]));
-    dv += g[c] * (gx * (t.t10[c] - t.t00[c]) + s.fx * (t.t11[c] - t.t01[c]));
-  }
-  du *= (float)Wl;
-  dv *= (float)Hl;
+  if (locate(q, Wl, Hl, s)) bilinear_duv<C, BOUND>(lvl, s, Wl, Hl, g, du, dv);
 }
 
 // ---- pyramid ----------------------------------------------------------------------------------------------------
@@ -160,10 +146,10 @@ __global__ __launch_bounds__(kTexThreads) void k_tex_mip_forward(MipArgs a, floa
     int l0;
     float f;
     level_of_detail(a.uv_da[i], a.Wt, a.Ht, a.L, l0, f);
-    bilinear<C, BOUND>(level_ptr<C>(tex, pyr, n0, l0), q, a.Wt >> l0, a.Ht >> l0, o);
+    level_value<C, BOUND>(level_ptr<C>(tex, pyr, n0, l0), q, a.Wt >> l0, a.Ht >> l0, o);
     if (f > 0.0f) {  // (then l0 + 1 <= L - 1: the clamp)
       float o1[C];
-      bilinear<C, BOUND>(level_ptr<C>(tex, pyr, n0, l0 + 1), q, a.Wt >> (l0 + 1), a.Ht >> (l0 + 1), o1);
+      level_value<C, BOUND>(level_ptr<C>(tex, pyr, n0, l0 + 1), q, a.Wt >> (l0 + 1), a.Ht >> (l0 + 1), o1);
 #pragma unroll
       for (int c = 0; c < C; ++c) o[c] = (1.0f - f) * o[c] + f * o1[c];
     }
@@ -172,19 +158,14 @@ __global__ __launch_bounds__(kTexThreads) void k_tex_mip_forward(MipArgs a, floa
 }
 
 // ---- backward ---------------------------------------------------------------------------------------------------
-template <int MODE>
-__device__ __forceinline__ void level_add(void *__restrict__ G, size_t k, float v, float to_fixed, int *overflow) {
-  if (MODE == kModeFloat) atomicAdd((float *)G + k, v);
-  else atomic_add_fixed((long long *)G + k, v, to_fixed, overflow);
-}
-
 // g0 / g1: the gradient pyramid's level 0 [Bt,Ht,Wt,C] and packed levels >= 1, float or 64-bit fixed point by MODE
 // (strides in elements per texture, 0 when shared); both null: d uv only
 template <int C, int BOUND, int MODE>
 __global__ __launch_bounds__(kTexThreads) void k_tex_mip_backward(MipArgs a, int tiles_x,
-                                                                 const float *__restrict__ dout, void *__restrict__ g0,
-                                                                 size_t g0_stride, void *__restrict__ g1,
-                                                                 size_t g1_stride, float2 *__restrict__ duv,
+                                                                 const float *__restrict__ dout,
+                                                                 Accum<MODE> *__restrict__ g0, size_t g0_stride,
+                                                                 Accum<MODE> *__restrict__ g1, size_t g1_stride,
+                                                                 float2 *__restrict__ duv,
                                                                  DetBlock *__restrict__ det_block) {
   __shared__ unsigned long long window[kMipWindowBytes / 8];
   __shared__ int box_part[kTexThreads / kWave][4];
@@ -227,11 +208,11 @@ __global__ __launch_bounds__(kTexThreads) void k_tex_mip_backward(MipArgs a, int
     if (duv) {
       float du = 0.0f, dv = 0.0f;
       if (ok[j]) {
-        bilinear_duv<C, BOUND>(level_ptr<C>(tex, pyr, n0, l0[j]), q[j], a.Wt >> l0[j], a.Ht >> l0[j], g[j], du, dv);
+        level_duv<C, BOUND>(level_ptr<C>(tex, pyr, n0, l0[j]), q[j], a.Wt >> l0[j], a.Ht >> l0[j], g[j], du, dv);
         if (f[j] > 0.0f) {
           float du1, dv1;
-          bilinear_duv<C, BOUND>(level_ptr<C>(tex, pyr, n0, l0[j] + 1), q[j], a.Wt >> (l0[j] + 1),
-                                 a.Ht >> (l0[j] + 1), g[j], du1, dv1);
+          level_duv<C, BOUND>(level_ptr<C>(tex, pyr, n0, l0[j] + 1), q[j], a.Wt >> (l0[j] + 1), a.Ht >> (l0[j] + 1),
+                              g[j], du1, dv1);
           du = (1.0f - f[j]) * du + f[j] * du1;
           dv = (1.0f - f[j]) * dv + f[j] * dv1;
         }
@@ -258,17 +239,15 @@ __global__ __launch_bounds__(kTexThreads) void k_tex_mip_backward(MipArgs a, int
 
   const float to_fixed = MODE == kModeFixed ? det_block->to_fixed : 0.0f;
   int *overflow = MODE == kModeFixed ? &det_block->overflow : nullptr;
-  constexpr int kCap = MODE == kModeFixed ? kMipWindowBytes / 8 : kMipWindowBytes / 4;
 
   for (int l = lmin; l <= lmax; ++l) {  // uniform: one pass per level
     const int Wl = a.Wt >> l, Hl = a.Ht >> l;
-    void *G = l == 0 ? g0 : g1;
+    Accum<MODE> *G = l == 0 ? g0 : g1;
     const size_t base = l == 0 ? (size_t)b * g0_stride : (size_t)b * g1_stride + mip_offset(n0, l) * C;
 
     Sample s[kTileRowsPerLane];
     bool on[kTileRowsPerLane];
     float gl[kTileRowsPerLane][C];  // level weight x dout
-    int bx0 = INT_MAX, bx1 = INT_MIN, by0 = INT_MAX, by1 = INT_MIN;
 #pragma unroll
     for (int j = 0; j < kTileRowsPerLane; ++j) {
       const bool lower = l0[j] == l, upper = l0[j] + 1 == l && f[j] > 0.0f;
@@ -277,127 +256,8 @@ __global__ __launch_bounds__(kTexThreads) void k_tex_mip_backward(MipArgs a, int
       const float lw = lower ? 1.0f - f[j] : f[j];
 #pragma unroll
       for (int c = 0; c < C; ++c) gl[j][c] = lw * g[j][c];
-      if (!on[j]) continue;
-      bx0 = min(bx0, box_index<BOUND>(s[j].x0, Wl));
-      bx1 = max(bx1, box_index<BOUND>(s[j].x0 + 1, Wl));
-      by0 = min(by0, box_index<BOUND>(s[j].y0, Hl));
-      by1 = max(by1, box_index<BOUND>(s[j].y0 + 1, Hl));
     }
-    bx0 = wave_min_i(bx0);
-    bx1 = wave_max_i(bx1);
-    by0 = wave_min_i(by0);
-    by1 = wave_max_i(by1);
-    if (lane == 0) {
-      box_part[wave][0] = bx0;
-      box_part[wave][1] = bx1;
-      box_part[wave][2] = by0;
-      box_part[wave][3] = by1;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int w = 0; w < kTexThreads / kWave; ++w) {
-      bx0 = min(bx0, box_part[w][0]);
-      bx1 = max(bx1, box_part[w][1]);
-      by0 = min(by0, box_part[w][2]);
-      by1 = max(by1, box_part[w][3]);
-    }
-    const int bw = bx1 - bx0 + 1, bh = by1 - by0 + 1;
-    if (bx0 > bx1) {
-      // no pixel of the tile at this level (uniform)
-    } else if ((long long)bw * bh * C <= kCap) {
-      // LDS window [bh][bw][C]
-      const int n = bw * bh * C, row = bw * C;
-      for (int k = (int)threadIdx.x; k < n; k += kTexThreads) {
-        if (MODE == kModeFixed) window[k] = 0ull;
-        else ((float *)window)[k] = 0.0f;
-      }
-      __syncthreads();
-#pragma unroll
-      for (int j = 0; j < kTileRowsPerLane; ++j) {
-        if (!on[j]) continue;
-        const int xa = box_index<BOUND>(s[j].x0, Wl) - bx0, xb = box_index<BOUND>(s[j].x0 + 1, Wl) - bx0;
-        const int ya = box_index<BOUND>(s[j].y0, Hl) - by0, yb = box_index<BOUND>(s[j].y0 + 1, Hl) - by0;
-        const float gx = 1.0f - s[j].fx, gy = 1.0f - s[j].fy;
-        const float w00 = gx * gy, w01 = s[j].fx * gy, w10 = gx * s[j].fy, w11 = s[j].fx * s[j].fy;
-#pragma unroll
-        for (int c = 0; c < C; ++c) {
-          window_add<MODE>(window, ya * row + xa * C + c, w00 * gl[j][c], to_fixed, overflow);
-          window_add<MODE>(window, ya * row + xb * C + c, w01 * gl[j][c], to_fixed, overflow);
-          window_add<MODE>(window, yb * row + xa * C + c, w10 * gl[j][c], to_fixed, overflow);
-          window_add<MODE>(window, yb * row + xb * C + c, w11 * gl[j][c], to_fixed, overflow);
-        }
-      }
-      __syncthreads();
-      // flush: consecutive threads take consecutive floats of a window row, i.e. of a level row (two segments
-      // where the row crosses the wrap seam); untouched cells are skipped
-      for (int k = (int)threadIdx.x; k < n; k += kTexThreads) {
-        const int r = k / row, rem = k - r * row;
-        const int col = rem / C, c = rem - col * C;
-        const size_t dst = base + ((size_t)tex_index<BOUND>(by0 + r, Hl) * Wl + tex_index<BOUND>(bx0 + col, Wl)) * C + c;
-        if (MODE == kModeFloat) {
-          const float v = ((const float *)window)[k];
-          if (v != 0.0f) atomicAdd((float *)G + dst, v);
-        } else {
-          const unsigned long long v = window[k];
-          if (v != 0ull) atomicAdd((unsigned long long *)G + dst, v);
-        }
-      }
-    } else {
-      // fallback: texel keys per contribution, a few leader rounds of wavefront pre-reduction, then per-lane atomics
-      int key[kTaps];
-      float wt[kTaps];
-#pragma unroll
-      for (int j = 0; j < kTileRowsPerLane; ++j) {
-        const int xa = tex_index<BOUND>(s[j].x0, Wl), xb = tex_index<BOUND>(s[j].x0 + 1, Wl);
-        const int ya = tex_index<BOUND>(s[j].y0, Hl), yb = tex_index<BOUND>(s[j].y0 + 1, Hl);
-        const float gx = 1.0f - s[j].fx, gy = 1.0f - s[j].fy;
-        key[4 * j + 0] = on[j] ? ya * Wl + xa : -1;  // < 2^28: abi.hip
-        key[4 * j + 1] = on[j] ? ya * Wl + xb : -1;
-        key[4 * j + 2] = on[j] ? yb * Wl + xa : -1;
-        key[4 * j + 3] = on[j] ? yb * Wl + xb : -1;
-        wt[4 * j + 0] = gx * gy;
-        wt[4 * j + 1] = s[j].fx * gy;
-        wt[4 * j + 2] = gx * s[j].fy;
-        wt[4 * j + 3] = s[j].fx * s[j].fy;
-      }
-      bool mine = false;
-#pragma unroll
-      for (int t = 0; t < kTaps; ++t) mine |= key[t] >= 0;
-      unsigned long long pending = __ballot(mine);
-      for (int round = 0; pending && round < kLeaderRounds; ++round) {  // wave-uniform
-        const int leader = __ffsll((long long)pending) - 1;
-        int first = -1;
-#pragma unroll
-        for (int t = kTaps - 1; t >= 0; --t) first = key[t] >= 0 ? key[t] : first;
-        const int K = __builtin_amdgcn_readlane(first, leader);
-        float sum[C];
-#pragma unroll
-        for (int c = 0; c < C; ++c) sum[c] = 0.0f;
-#pragma unroll
-        for (int t = 0; t < kTaps; ++t) {
-          if (key[t] != K) continue;
-#pragma unroll
-          for (int c = 0; c < C; ++c) sum[c] += wt[t] * gl[t / 4][c];
-          key[t] = -1;
-        }
-#pragma unroll
-        for (int c = 0; c < C; ++c) sum[c] = wave_sum_f(sum[c]);
-        if (lane == leader) {
-#pragma unroll
-          for (int c = 0; c < C; ++c) level_add<MODE>(G, base + (size_t)K * C + c, sum[c], to_fixed, overflow);
-        }
-        mine = false;
-#pragma unroll
-        for (int t = 0; t < kTaps; ++t) mine |= key[t] >= 0;
-        pending = __ballot(mine);
-      }
-#pragma unroll
-      for (int t = 0; t < kTaps; ++t) {
-        if (key[t] < 0) continue;
-#pragma unroll
-        for (int c = 0; c < C; ++c) level_add<MODE>(G, base + (size_t)key[t] * C + c, wt[t] * gl[t / 4][c], to_fixed, overflow);
-      }
-    }
+    scatter_level<C, BOUND, MODE, kMipWindowBytes>(window, box_part, s, on, gl, Wl, Hl, G, base, to_fixed, overflow);
     __syncthreads();  // the next level's pass reuses box_part and the window
   }
 }
@@ -507,8 +367,7 @@ MipArgs make_args(const float *tex, const float *pyr, int tex_batched, int Ht, i
   return a;
 }
 
-template <int C>
-int launch_build_c(const float *tex, int tex_batched, int Ht, int Wt, int L, int B, float *pyr, hipStream_t s) {
+int launch_build(const float *tex, int tex_batched, int Ht, int Wt, int C, int L, int B, float *pyr, hipStream_t s) {
   const size_t n0 = (size_t)Ht * Wt, count = count_of(tex_batched, B);
   const size_t pyr_stride = mip_stride(n0, L) * C;
   for (int l = 0; l + 1 < L; ++l) {
@@ -516,65 +375,43 @@ int launch_build_c(const float *tex, int tex_batched, int Ht, int Wt, int L, int
     const size_t src_stride = l == 0 ? n0 * C : pyr_stride;
     const int Ws = Wt >> l, Wd = Wt >> (l + 1), n_dst = Wd * (Ht >> (l + 1));
     const dim3 grid((unsigned)((n_dst + kTexThreads - 1) / kTexThreads), (unsigned)count), block(kTexThreads);
-    hipLaunchKernelGGL((k_mip_build<C>), grid, block, 0, s, src, src_stride, pyr + mip_offset(n0, l + 1) * C, pyr_stride,
-                       Ws, Wd, n_dst);
+    with_channels(C, [&](auto c) {
+      hipLaunchKernelGGL((k_mip_build<decltype(c)::value>), grid, block, 0, s, src, src_stride,
+                         pyr + mip_offset(n0, l + 1) * C, pyr_stride, Ws, Wd, n_dst);
+    });
     const int rc = check_launch();
     if (rc != MR_OK) return rc;
   }
   return MR_OK;
 }
 
-template <int C>
-int launch_forward_c(const MipArgs &a, int B, int boundary, float *out, hipStream_t s) {
-  const dim3 grid((unsigned)(((size_t)a.W * a.H + kTexThreads - 1) / kTexThreads), (unsigned)B), block(kTexThreads);
-  if (boundary == MR_TEXTURE_WRAP) hipLaunchKernelGGL((k_tex_mip_forward<C, MR_TEXTURE_WRAP>), grid, block, 0, s, a, out);
-  else hipLaunchKernelGGL((k_tex_mip_forward<C, MR_TEXTURE_CLAMP>), grid, block, 0, s, a, out);
-  return check_launch();
-}
-
-template <int C, int MODE>
-int launch_backward_c(const MipArgs &a, int B, int boundary, const float *dout, void *g0, size_t g0_stride, void *g1,
-                      size_t g1_stride, float *duv, DetBlock *det_block, hipStream_t s) {
+template <int MODE>
+int launch_backward(const MipArgs &a, int C, int B, int boundary, const float *dout, Accum<MODE> *g0, size_t g0_stride,
+                    Accum<MODE> *g1, size_t g1_stride, float *duv, DetBlock *det_block, hipStream_t s) {
   const int tiles_x = (a.W + kTileW - 1) / kTileW, tiles_y = (a.H + kTileH - 1) / kTileH;
   const dim3 grid((unsigned)((size_t)tiles_x * tiles_y), (unsigned)B), block(kTexThreads);
-  if (boundary == MR_TEXTURE_WRAP)
-    hipLaunchKernelGGL((k_tex_mip_backward<C, MR_TEXTURE_WRAP, MODE>), grid, block, 0, s, a, tiles_x, dout, g0,
-                       g0_stride, g1, g1_stride, (float2 *)duv, det_block);
-  else
-    hipLaunchKernelGGL((k_tex_mip_backward<C, MR_TEXTURE_CLAMP, MODE>), grid, block, 0, s, a, tiles_x, dout, g0,
-                       g0_stride, g1, g1_stride, (float2 *)duv, det_block);
+  with_channels(C, [&](auto c) {
+    constexpr int kC = decltype(c)::value;
+    if (boundary == MR_TEXTURE_WRAP)
+      hipLaunchKernelGGL((k_tex_mip_backward<kC, MR_TEXTURE_WRAP, MODE>), grid, block, 0, s, a, tiles_x, dout, g0,
+                         g0_stride, g1, g1_stride, (float2 *)duv, det_block);
+    else
+      hipLaunchKernelGGL((k_tex_mip_backward<kC, MR_TEXTURE_CLAMP, MODE>), grid, block, 0, s, a, tiles_x, dout, g0,
+                         g0_stride, g1, g1_stride, (float2 *)duv, det_block);
+  });
   return check_launch();
 }
 
-template <int C, int MODE>
-int launch_fold_c(const void *g0, const void *g1, size_t g1_stride, const DetBlock *det_block, int Ht, int Wt, int L,
-                  size_t count, float *dtex, hipStream_t s) {
+template <int MODE>
+int launch_fold(int C, const void *g0, const void *g1, size_t g1_stride, const DetBlock *det_block, int Ht, int Wt,
+                int L, size_t count, float *dtex, hipStream_t s) {
   const size_t n0 = (size_t)Ht * Wt;
   const dim3 grid((unsigned)((n0 + kTexThreads - 1) / kTexThreads), (unsigned)count), block(kTexThreads);
-  hipLaunchKernelGGL((k_mip_fold<C, MODE>), grid, block, 0, s, g0, g1, g1_stride, det_block, Ht, Wt, L, dtex);
+  with_channels(C, [&](auto c) {
+    hipLaunchKernelGGL((k_mip_fold<decltype(c)::value, MODE>), grid, block, 0, s, g0, g1, g1_stride, det_block, Ht, Wt,
+                       L, dtex);
+  });
   return check_launch();
-}
-
-template <int MODE>
-int launch_backward_mode(const MipArgs &a, int C, int B, int boundary, const float *dout, void *g0, size_t g0_stride,
-                         void *g1, size_t g1_stride, float *duv, DetBlock *det_block, hipStream_t s) {
-  switch (C) {
-    case 1: return launch_backward_c<1, MODE>(a, B, boundary, dout, g0, g0_stride, g1, g1_stride, duv, det_block, s);
-    case 2: return launch_backward_c<2, MODE>(a, B, boundary, dout, g0, g0_stride, g1, g1_stride, duv, det_block, s);
-    case 3: return launch_backward_c<3, MODE>(a, B, boundary, dout, g0, g0_stride, g1, g1_stride, duv, det_block, s);
-    default: return launch_backward_c<4, MODE>(a, B, boundary, dout, g0, g0_stride, g1, g1_stride, duv, det_block, s);
-  }
-}
-
-template <int MODE>
-int launch_fold_mode(int C, const void *g0, const void *g1, size_t g1_stride, const DetBlock *det_block, int Ht, int Wt,
-                     int L, size_t count, float *dtex, hipStream_t s) {
-  switch (C) {
-    case 1: return launch_fold_c<1, MODE>(g0, g1, g1_stride, det_block, Ht, Wt, L, count, dtex, s);
-    case 2: return launch_fold_c<2, MODE>(g0, g1, g1_stride, det_block, Ht, Wt, L, count, dtex, s);
-    case 3: return launch_fold_c<3, MODE>(g0, g1, g1_stride, det_block, Ht, Wt, L, count, dtex, s);
-    default: return launch_fold_c<4, MODE>(g0, g1, g1_stride, det_block, Ht, Wt, L, count, dtex, s);
-  }
 }
 
 }  // namespace
@@ -599,21 +436,16 @@ int launch_texture_mip_forward(const float *tex, int tex_batched, int Ht, int Wt
                                const float *uv_da, const float *mask, int B, int W, int H, int boundary, float *pyr,
                                float *out, hipStream_t s) {
   if (B == 0) return MR_OK;
-  int rc;
-  switch (C) {
-    case 1: rc = launch_build_c<1>(tex, tex_batched, Ht, Wt, L, B, pyr, s); break;
-    case 2: rc = launch_build_c<2>(tex, tex_batched, Ht, Wt, L, B, pyr, s); break;
-    case 3: rc = launch_build_c<3>(tex, tex_batched, Ht, Wt, L, B, pyr, s); break;
-    default: rc = launch_build_c<4>(tex, tex_batched, Ht, Wt, L, B, pyr, s); break;
-  }
+  const int rc = launch_build(tex, tex_batched, Ht, Wt, C, L, B, pyr, s);
   if (rc != MR_OK || !out) return rc;  // out null: the pyramid alone
   const MipArgs a = make_args(tex, pyr, tex_batched, Ht, Wt, C, L, uv, uv_da, mask, W, H);
-  switch (C) {
-    case 1: return launch_forward_c<1>(a, B, boundary, out, s);
-    case 2: return launch_forward_c<2>(a, B, boundary, out, s);
-    case 3: return launch_forward_c<3>(a, B, boundary, out, s);
-    default: return launch_forward_c<4>(a, B, boundary, out, s);
-  }
+  const dim3 grid((unsigned)(((size_t)W * H + kTexThreads - 1) / kTexThreads), (unsigned)B), block(kTexThreads);
+  with_channels(C, [&](auto c) {
+    constexpr int kC = decltype(c)::value;
+    if (boundary == MR_TEXTURE_WRAP) hipLaunchKernelGGL((k_tex_mip_forward<kC, MR_TEXTURE_WRAP>), grid, block, 0, s, a, out);
+    else hipLaunchKernelGGL((k_tex_mip_forward<kC, MR_TEXTURE_CLAMP>), grid, block, 0, s, a, out);
+  });
+  return check_launch();
 }
 
 int launch_texture_mip_backward(const float *dout, const float *tex, const float *pyr, int tex_batched, int Ht, int Wt,
@@ -622,31 +454,28 @@ int launch_texture_mip_backward(const float *dout, const float *tex, const float
   if (B == 0 || (!dtex && !duv)) return MR_OK;
   const MipArgs a = make_args(tex, pyr, tex_batched, Ht, Wt, C, L, uv, uv_da, mask, W, H);
   const size_t count = count_of(tex_batched, B), n0 = (size_t)Ht * Wt, np = mip_stride(n0, L);
-  if (!dtex) return launch_backward_mode<kModeFloat>(a, C, B, boundary, dout, nullptr, 0, nullptr, 0, duv, nullptr, s);
+  if (!dtex) return launch_backward<kModeFloat>(a, C, B, boundary, dout, nullptr, 0, nullptr, 0, duv, nullptr, s);
   if (g_deterministic == 0) {
     // level 0 of the gradient pyramid is dtex itself, the packed levels >= 1 are the workspace
     float *g1 = (float *)ws;
     if (zero_async(dtex, count * n0 * C * sizeof(float), s) != hipSuccess) return check_launch();
     if (zero_async(g1, count * np * C * sizeof(float), s) != hipSuccess) return check_launch();
-    const int rc = launch_backward_mode<kModeFloat>(a, C, B, boundary, dout, dtex, a.tex_stride, g1, a.pyr_stride, duv,
-                                                    nullptr, s);
+    const int rc = launch_backward<kModeFloat>(a, C, B, boundary, dout, dtex, a.tex_stride, g1, a.pyr_stride, duv,
+                                               nullptr, s);
     if (rc != MR_OK || L == 1) return rc;
-    return launch_fold_mode<kModeFloat>(C, dtex, g1, np * C, nullptr, Ht, Wt, L, count, dtex, s);
+    return launch_fold<kModeFloat>(C, dtex, g1, np * C, nullptr, Ht, Wt, L, count, dtex, s);
   }
-  // Deterministic: every contribution is w * dout with w <= 1 (tap weight x level weight), so the scale comes from
-  // the largest |dout| and the number of pixels that sample one texture, as in the bilinear backward; the fold
-  // converts each level's sums and adds them in a fixed order.
+  // Deterministic: the whole gradient pyramid as 64-bit sums in the workspace, scaled by launch_texture_det_scale;
+  // the fold converts each level's sums and adds them in a fixed order.
   const size_t fixed_bytes = align_up(count * (n0 + np) * C * sizeof(long long), 256);
-  long long *f0 = (long long *)ws, *f1 = f0 + count * n0 * C;
+  unsigned long long *f0 = (unsigned long long *)ws, *f1 = f0 + count * n0 * C;
   DetBlock *det_block = (DetBlock *)((char *)ws + fixed_bytes);
   if (zero_async(f0, fixed_bytes, s) != hipSuccess) return check_launch();
-  const double per_texture = (double)(tex_batched ? 1 : B) * W * H;
-  const float gain = (float)fmax(1.0, per_texture / (double)(1 << 21));
-  int rc = launch_det_scale(dout, (size_t)B * W * H * C, gain, det_block, s);
+  int rc = launch_texture_det_scale(dout, tex_batched, B, W, H, C, det_block, s);
   if (rc != MR_OK) return rc;
-  rc = launch_backward_mode<kModeFixed>(a, C, B, boundary, dout, f0, a.tex_stride, f1, a.pyr_stride, duv, det_block, s);
+  rc = launch_backward<kModeFixed>(a, C, B, boundary, dout, f0, a.tex_stride, f1, a.pyr_stride, duv, det_block, s);
   if (rc != MR_OK) return rc;
-  return launch_fold_mode<kModeFixed>(C, f0, f1, np * C, det_block, Ht, Wt, L, count, dtex, s);
+  return launch_fold<kModeFixed>(C, f0, f1, np * C, det_block, Ht, Wt, L, count, dtex, s);
 }
 
 int launch_attribute_derivatives(const int32_t *ids, const float *bary, const float *clip, const int32_t *tris,
@@ -654,16 +483,10 @@ int launch_attribute_derivatives(const int32_t *ids, const float *bary, const fl
                                  int H, int A, float *out, hipStream_t s) {
   if (B == 0) return MR_OK;
   const dim3 grid((unsigned)(((size_t)W * H + kTexThreads - 1) / kTexThreads), (unsigned)B), block(kTexThreads);
-#define MR_LAUNCH_DERIVATIVES(N)                                                                                     \
-  hipLaunchKernelGGL((k_attr_derivatives<N>), grid, block, 0, s, ids, bary, (const float4 *)clip, tris, attrs,      \
-                     attr_tris, V, T, Va, W, H, (float2 *)out)
-  switch (A) {
-    case 1: MR_LAUNCH_DERIVATIVES(1); break;
-    case 2: MR_LAUNCH_DERIVATIVES(2); break;
-    case 3: MR_LAUNCH_DERIVATIVES(3); break;
-    default: MR_LAUNCH_DERIVATIVES(4); break;
-  }
-#undef MR_LAUNCH_DERIVATIVES
+  with_channels(A, [&](auto n) {
+    hipLaunchKernelGGL((k_attr_derivatives<decltype(n)::value>), grid, block, 0, s, ids, bary, (const float4 *)clip,
+                       tris, attrs, attr_tris, V, T, Va, W, H, (float2 *)out);
+  });
   return check_launch();
 }
 

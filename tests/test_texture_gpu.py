@@ -135,6 +135,24 @@ def test_a_huge_texture_under_random_uvs_takes_the_fallback():
     _check_gradients(tex, uv, _mask(B, H, W, 93), "clamp", dout)
 
 
+@pytest.mark.parametrize("C, boundary", itertools.product([1, 2, 4], ["wrap", "clamp"]))
+def test_the_fallback_at_every_other_channel_count(C, boundary):
+    # one 64 x 16 tile of uniform random UVs over 256^2 texels: its tap box x C is above the LDS window in float and
+    # in fixed point, so the leader rounds and the per-lane atomics (unrolled per channel) do all of the scatter
+    B, H, W, S = 1, 16, 64, 256
+    tex = _tex(False, B, S, S, C, 94)
+    uv = torch.rand(B, H, W, 2, generator=torch.Generator().manual_seed(95)).to(DEV)
+    dout = torch.randn(B, H, W, C, generator=torch.Generator().manual_seed(96)).to(DEV)
+    used, cells = _tile_cells(uv.cpu(), None, S, S, C, boundary)
+    assert used.shape == (1, 1, 1) and bool(used.all()) and int(cells.min()) > 8192
+    _check_gradients(tex, uv, None, boundary, dout)
+    before = _native.set_deterministic(True)
+    try:
+        _check_gradients(tex, uv, None, boundary, dout)
+    finally:
+        _native.set_deterministic(before)
+
+
 @pytest.mark.parametrize("batched", [False, True])
 def test_tiles_straddling_the_wrap_seam(batched):
     B, H, W, Ht, Wt = 8, 96, 200, 48, 64
@@ -171,10 +189,10 @@ def test_full_size_texture_gradient():
     assert bool((err <= 1e-5 * abs_sum).all()), float((err - 1e-5 * abs_sum).max())
 
 
-def _tile_paths(uv, mask, Ht, Wt, C, boundary):
-    """The backward's 64 x 16 pixel tiles (csrc/texture.hip) -> (tiles that sample any texel, those whose tap box
-    x C fits the float LDS window (8192 cells), those whose box fits the fixed-point window (4096 cells)); the rest
-    take the per-lane fallback.  The box is in unwrapped texel indices under wrap, clamped ones under clamp."""
+def _tile_cells(uv, mask, Ht, Wt, C, boundary):
+    """The backward's 64 x 16 pixel tiles (csrc/texture_taps.h: scatter_level) -> (which tiles sample any texel, each
+    tile's tap box x C in cells), from the restatement's taps.  The box is in unwrapped texel indices under wrap,
+    clamped ones under clamp."""
     valid = ref.taps(uv, Ht, Wt, mask, boundary)[0]
     x, y = ref._coords(uv, Ht, Wt)
     x0 = torch.floor(torch.where(valid, x, torch.zeros_like(x))).long()
@@ -192,8 +210,13 @@ def _tile_paths(uv, mask, Ht, Wt, C, boundary):
         return t.view(B, (H + ph) // 16, 16, (W + pw) // 64, 64)
     bx0, by0 = tiles(lo_x, big).amin((2, 4)), tiles(lo_y, big).amin((2, 4))
     bx1, by1 = tiles(hi_x, -big).amax((2, 4)), tiles(hi_y, -big).amax((2, 4))
-    used = bx0 <= bx1
-    cells = (bx1 - bx0 + 1) * (by1 - by0 + 1) * C
+    return bx0 <= bx1, (bx1 - bx0 + 1) * (by1 - by0 + 1) * C
+
+
+def _tile_paths(uv, mask, Ht, Wt, C, boundary):
+    """-> (tiles that sample any texel, those whose tap box x C fits the bilinear backward's float LDS window (32 KiB:
+    8192 cells), those whose box fits its fixed-point window (4096 cells)); the rest take the per-lane fallback."""
+    used, cells = _tile_cells(uv, mask, Ht, Wt, C, boundary)
     return int(used.sum()), int((used & (cells <= 8192)).sum()), int((used & (cells <= 4096)).sum())
 
 

@@ -17,7 +17,7 @@ from conftest import golden_npz
 from pytorch_mesh_renderer_amd import _native, mesh_renderer
 from pytorch_mesh_renderer_amd.common import camera_utils, shapes
 from pytorch_mesh_renderer_amd.mesh_renderer.rasterize_triangles_ext import AttributeInterpolator, BarycentricRasterizer
-from test_texture_gpu import _mask, _tex, _uv
+from test_texture_gpu import _mask, _tex, _tile_cells, _uv
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
@@ -192,6 +192,26 @@ def test_a_huge_texture_under_random_uvs_takes_the_fallback():
     _check_gradients(tex, uv, uv_da, None, "wrap", dout)
     # lod clamped at 0 by a capped pyramid: the scatter goes to level 0 itself, all of it
     _check_gradients(tex, uv, uv_da, _mask(B, H, W, 93), "clamp", dout, max_mip_level=0)
+
+
+@pytest.mark.parametrize("C, boundary", itertools.product([1, 2, 4], ["wrap", "clamp"]))
+def test_the_fallback_at_every_other_channel_count(C, boundary):
+    # one 64 x 16 tile of uniform random UVs over 256^2 texels with zero derivatives (lod 0: the scatter lands on
+    # level 0): its tap box x C is above the 60 KiB LDS window (15360 float cells) in float and in fixed point, so the
+    # leader rounds and the per-lane atomics (unrolled per channel) do all of the scatter
+    B, H, W, S = 1, 16, 64, 256
+    tex = _tex(False, B, S, S, C, 94)
+    uv = torch.rand(B, H, W, 2, generator=torch.Generator().manual_seed(95)).to(DEV)
+    uv_da = torch.zeros(B, H, W, 4, device=DEV)
+    dout = torch.randn(B, H, W, C, generator=torch.Generator().manual_seed(96)).to(DEV)
+    used, cells = _tile_cells(uv.cpu(), None, S, S, C, boundary)
+    assert used.shape == (1, 1, 1) and bool(used.all()) and int(cells.min()) > 15360
+    _check_gradients(tex, uv, uv_da, None, boundary, dout)
+    before = _native.set_deterministic(True)
+    try:
+        _check_gradients(tex, uv, uv_da, None, boundary, dout)
+    finally:
+        _native.set_deterministic(before)
 
 
 @pytest.mark.parametrize("batched", [False, True])
