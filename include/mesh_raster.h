@@ -731,6 +731,51 @@ int mr_mesh_regularizer_backward(const float *dterms, const float *vertices, con
                                  const int32_t *role_offsets, const int32_t *roles, int B, int V, int E, int F,
                                  int terms, int use_target, float target_length, float *dvertices, void *stream);
 
+/* ---- nearest neighbours between point clouds: the Chamfer distance (no reference counterpart) ----
+ * Per image b, for every query x_i with i < x_lengths[b], over the targets y_j with j < y_lengths[b]
+ * ("Point-cloud losses"):
+ *   sqdist_i = min_j (x_i - y_j).(x_i - y_j)   in this difference form, never |x|^2 + |y|^2 - 2 x.y
+ *   idx_i    = the LOWEST j that attains it (equal float32 distances), whatever the launch shape
+ * A padded query (i >= x_lengths[b]) and every query of an image without targets get sqdist 0, idx -1.  Every idx
+ * written for a valid query with a non-empty target lies in [0, y_lengths[b]), also when coordinates are NaN or
+ * infinite (a distance that is NaN never wins; a query whose distances are all NaN gets sqdist +inf).
+ *   x [B,N,3], y [B,M,3] f32;  x_lengths, y_lengths [B] i32 (device) or NULL = all N / all M; clamped to [0, N] /
+ *   [0, M] by the kernels
+ *   sqdist [B,N] f32 out or NULL;  idx [B,N] i32 out
+ *   total  [B] f32 or NULL: total[b] = (accumulate ? total[b] : 0) + weight * (mean of sqdist over image b's valid
+ *          queries; 0 when either side is empty) -- a fixed-order sum of per-workgroup partials, so Chamfer's two
+ *          directions are two calls, the second with accumulate = 1
+ * mr_nearest_plan: the launch shape of these sizes, a pure host function (nothing touches a device): the target
+ * range is cut into `splits` runs of whole `target_tile`s (one workgroup of `workgroup_size` threads per run and
+ * `queries_per_lane` x `workgroup_size` queries; with splits > 1 each writes a 64-bit key (distance bits << 32) |
+ * index per query into the workspace and a second pass takes the unsigned minimum: order-independent, no atomics).
+ * The workspace holds those keys and the partial sums; it is needed by every call (>= 256 bytes).
+ *
+ * mr_nearest_backward: the gradient of  sum_i g_i sqdist_i  of the directions that ran, to both clouds in one call:
+ *   direction x -> y (idx_xy [B,N] non-NULL): dx_i += 2 g_i (x_i - y_idx_i),  dy_j -= sum_{i: idx_i = j} 2 g_i (x_i - y_j)
+ *   direction y -> x (idx_yx [B,M] non-NULL): the same with the clouds exchanged
+ *   g_i = grad_points[b,i]  (per point, [B,N], x -> y alone), or with grad_images [B]:
+ *         grad_images[b] * x_weight / valid queries of x  (x -> y),   grad_images[b] * y_weight / valid y  (y -> x)
+ *   order_xy [B,N], offsets_xy [B,M+1] i32: the inverted index of idx_xy -- per image the queries i grouped by their
+ *         idx_i in ascending j, each group in a FIXED order (a stable sort of idx with -1 last), group j at
+ *         order_xy[b, offsets_xy[b,j] .. offsets_xy[b,j+1]); needed when dy is asked for.  order_yx [B,M],
+ *         offsets_yx [B,N+1] likewise for dx.
+ *   dx [B,N,3], dy [B,M,3] f32 out or NULL (not computed); each is written completely, padded rows 0
+ * Exactly one of grad_points / grad_images.  Gather form over the inverted index, eight lanes per destination point
+ * and a fixed butterfly: no atomics, no zero-fills, bit-reproducible in either deterministic mode.  An index outside
+ * the other cloud in idx or order is skipped.
+ * 1 <= B <= 65535, 1 <= N, M <= 2^28, B * N and B * M below 2^36; sizes outside are MR_EINVAL (queries return 0). */
+int mr_nearest_plan(int B, int N, int M, int *splits, int *queries_per_lane, int *target_tile, int *workgroup_size);
+size_t mr_nearest_workspace_bytes(int B, int N, int M);
+int mr_nearest_forward(const float *x, const float *y, const int32_t *x_lengths, const int32_t *y_lengths, int B, int N,
+                       int M, float *sqdist, int32_t *idx, float *total, float weight, int accumulate, void *workspace,
+                       size_t workspace_bytes, void *stream);
+int mr_nearest_backward(const float *x, const float *y, const int32_t *x_lengths, const int32_t *y_lengths, int B, int N,
+                        int M, const int32_t *idx_xy, const int32_t *order_xy, const int32_t *offsets_xy,
+                        const int32_t *idx_yx, const int32_t *order_yx, const int32_t *offsets_yx,
+                        const float *grad_points, const float *grad_images, float x_weight, float y_weight, float *dx,
+                        float *dy, void *stream);
+
 /* ---- clip-space transforms --------------------------------------------------------------
  * perspective(aspect, fov_y, near, far) . look_at(eye, center, up) per image, the product render() and
  * rasterize() apply to the vertices (src/common/camera_utils.py:45-139; src/mesh_renderer/render.py
@@ -777,7 +822,7 @@ int mr_tone_map(const float *image, int B, size_t elements_per_image, float gamm
  * number.  mr_soft_backward is covered as well (fixed-point integer atomics into 64-bit copies of its
  * four vertex outputs, scaled for the 1 / sigma and 1 / gamma its contributions carry; its light
  * gradients are fixed-order sums in either mode).  mr_antialias_backward is covered (fixed-point integer atomics for dclip, scaled from a first pass that finds
- * its largest per-vertex contribution).  mr_sh_shade_backward has no atomics and is bit-reproducible in either mode, and so are mr_mesh_regularizer_forward / _backward and mr_ssim_forward / _backward.  mr_texture_backward is covered (fixed-point integer adds, in LDS and in the workspace, for dtex, scaled from a first pass that finds the largest upstream gradient and from the number of pixels that sample one texture; duv is per pixel in either mode), and so is mr_texture_mip_backward (the same fixed-point scatter into every level of the gradient pyramid, the same scale rule -- a contribution is level weight x tap weight x dout, at most |dout| -- then one gathered pass that converts each level's sums and folds them in a fixed order).  mr_texture_mip_forward and mr_attribute_derivatives have no atomics.  Not covered, float atomics remain: the composed
+ * its largest per-vertex contribution).  mr_sh_shade_backward has no atomics and is bit-reproducible in either mode, and so are mr_mesh_regularizer_forward / _backward, mr_ssim_forward / _backward and mr_nearest_forward / _backward.  mr_texture_backward is covered (fixed-point integer adds, in LDS and in the workspace, for dtex, scaled from a first pass that finds the largest upstream gradient and from the number of pixels that sample one texture; duv is per pixel in either mode), and so is mr_texture_mip_backward (the same fixed-point scatter into every level of the gradient pyramid, the same scale rule -- a contribution is level weight x tap weight x dout, at most |dout| -- then one gathered pass that converts each level's sums and folds them in a fixed order).  mr_texture_mip_forward and mr_attribute_derivatives have no atomics.  Not covered, float atomics remain: the composed
  * interpolation backward (mr_interpolate_backward, the path for more than 16 attributes).  mr_l1_loss_forward is always deterministic.  Returns the previous setting. */
 int mr_set_deterministic(int on);
 

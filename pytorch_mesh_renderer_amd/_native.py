@@ -332,6 +332,18 @@ def lib():
         except AttributeError as e:   # the SSIM entry points came without an ABI version bump
             raise NativeLibraryError("%s lacks the SSIM entry points (%s): rebuild it (make -C "
                                      "pytorch_mesh_renderer_amd/csrc)" % (LIB_PATH, e))
+        try:
+            L.mr_nearest_plan.argtypes = [ci] * 3 + [vp] * 4
+            L.mr_nearest_plan.restype = ci
+            L.mr_nearest_workspace_bytes.argtypes = [ci] * 3
+            L.mr_nearest_workspace_bytes.restype = sz
+            L.mr_nearest_forward.argtypes = [vp] * 4 + [ci] * 3 + [vp, vp, vp, cf, ci, vp, sz, vp]
+            L.mr_nearest_forward.restype = ci
+            L.mr_nearest_backward.argtypes = [vp] * 4 + [ci] * 3 + [vp] * 8 + [cf, cf, vp, vp, vp]
+            L.mr_nearest_backward.restype = ci
+        except AttributeError as e:   # the point-cloud entry points came without an ABI version bump
+            raise NativeLibraryError("%s lacks the nearest-neighbour entry points (%s): rebuild it (make -C "
+                                     "pytorch_mesh_renderer_amd/csrc)" % (LIB_PATH, e))
         _lib = L
     return _lib
 
@@ -984,6 +996,108 @@ def mesh_regularizer_backward(dterms, vertices, unit_dirs, topology, terms, targ
             _ptr(dvertices), _stream(dev))
     _check(rc, "mr_mesh_regularizer_backward")
     return dvertices
+
+
+def nearest_plan(B, N, M):
+    """The launch shape mr_nearest_forward takes for B images of N queries against M targets, a pure host function:
+    {"splits", "queries_per_lane", "target_tile", "workgroup_size"} (include/mesh_raster.h)."""
+    out = (ctypes.c_int * 4)()
+    rc = lib().mr_nearest_plan(int(B), int(N), int(M), *[ctypes.c_void_p(ctypes.addressof(out) + 4 * k) for k in range(4)])
+    if rc != MR_OK:
+        raise ValueError("nearest_plan takes 1..65535 images of 1..2^28 points, got (%r, %r, %r)" % (B, N, M))
+    return dict(zip(("splits", "queries_per_lane", "target_tile", "workgroup_size"), list(out)))
+
+
+def _chk_clouds(x, y, x_lengths, y_lengths):
+    _chk("x", x, _F32, None, None, 3)
+    B, N, _ = x.shape
+    _chk("y", y, _F32, B, None, 3)
+    M = y.shape[1]
+    if not 1 <= B <= 65535 or not 1 <= N <= 1 << 28 or not 1 <= M <= 1 << 28 or B * N >= 1 << 36 or B * M >= 1 << 36:
+        raise ValueError("the point-cloud kernels take 1..65535 images of 1..2^28 points, got %s and %s"
+                         % (list(x.shape), list(y.shape)))
+    for name, t in (("x_lengths", x_lengths), ("y_lengths", y_lengths)):
+        if t is not None:
+            _chk(name, t, _I32, B)
+    return B, N, M
+
+
+def nearest_forward(x, y, x_lengths=None, y_lengths=None, want_sqdist=True, total=None, weight=1.0):
+    """x [B,N,3], y [B,M,3] f32, lengths [B] i32 or None (device) -> (sqdist [B,N] f32 or None, idx [B,N] i32,
+    total [B] f32 or None): mr_nearest_forward.  total: None = no mean; True = a fresh [B] tensor set to weight *
+    mean; a [B] tensor = weight * mean is added to it (Chamfer's second direction)."""
+    B, N, M = _chk_clouds(x, y, x_lengths, y_lengths)
+    given = [t for t in (x_lengths, y_lengths) if t is not None]
+    accumulate = torch.is_tensor(total)
+    if accumulate:
+        _chk("total", total, _F32, B)
+        if not total.is_contiguous():
+            raise ValueError("total must be contiguous")
+        given.append(total)
+    dev = _require_device(x, y, *given)
+    L = lib()
+    x, y = x.contiguous(), y.contiguous()
+    x_lengths = x_lengths.contiguous() if x_lengths is not None else None
+    y_lengths = y_lengths.contiguous() if y_lengths is not None else None
+    sqdist = torch.empty(B, N, dtype=_F32, device=dev) if want_sqdist else None
+    idx = torch.empty(B, N, dtype=_I32, device=dev)
+    if total is True:
+        total = torch.empty(B, dtype=_F32, device=dev)
+    with torch.cuda.device(dev):
+        ws, have = _workspace(dev, L.mr_nearest_workspace_bytes(B, N, M))
+        rc = L.mr_nearest_forward(_ptr(x), _ptr(y), _ptr(x_lengths), _ptr(y_lengths), B, N, M, _ptr(sqdist), _ptr(idx),
+                                  _ptr(total), float(weight), 1 if accumulate else 0, _ptr(ws), have, _stream(dev))
+    _check(rc, "mr_nearest_forward")
+    return sqdist, idx, total
+
+
+def nearest_inverted_index(idx, targets):
+    """idx [B,Q] i32 (-1 = no neighbour) into `targets` points -> (order [B,Q] i32, offsets [B,targets+1] i32): per
+    image the queries grouped by the target they chose, each group in ascending query order (a STABLE sort, so the
+    backward's sums have a fixed order), group j at order[b, offsets[b,j]:offsets[b,j+1]]; queries without a neighbour
+    come after offsets[b,targets].  Device-side torch ops (sort + searchsorted), no host synchronisation."""
+    _chk("idx", idx, _I32, None, None)
+    key = torch.where(idx < 0, torch.full_like(idx, targets), idx)
+    sorted_key, order = torch.sort(key, dim=1, stable=True)
+    bounds = torch.arange(targets + 1, dtype=_I32, device=idx.device).unsqueeze(0).expand(idx.shape[0], -1).contiguous()
+    offsets = torch.searchsorted(sorted_key, bounds, out_int32=True)
+    return order.to(_I32), offsets
+
+
+def nearest_backward(x, y, x_lengths, y_lengths, idx_xy=None, index_xy=None, idx_yx=None, index_yx=None,
+                     grad_points=None, grad_images=None, x_weight=1.0, y_weight=1.0, want_dx=True, want_dy=True):
+    """mr_nearest_backward -> (dx [B,N,3] or None, dy [B,M,3] or None).  idx_xy / idx_yx: the saved indices of the
+    directions that ran; index_xy / index_yx: their nearest_inverted_index(), needed for dy / dx respectively."""
+    B, N, M = _chk_clouds(x, y, x_lengths, y_lengths)
+    tensors = [x, y] + [t for t in (x_lengths, y_lengths) if t is not None]
+    for name, idx, index, Q, T in (("xy", idx_xy, index_xy, N, M), ("yx", idx_yx, index_yx, M, N)):
+        if idx is not None:
+            _chk("idx_" + name, idx, _I32, B, Q)
+            tensors.append(idx)
+        if index is not None:
+            _chk("order_" + name, index[0], _I32, B, Q)
+            _chk("offsets_" + name, index[1], _I32, B, T + 1)
+            tensors += list(index)
+    if grad_points is not None:
+        _chk("upstream gradient", grad_points, _F32, B, N)
+        tensors.append(grad_points)
+    if grad_images is not None:
+        _chk("upstream gradient", grad_images, _F32, B)
+        tensors.append(grad_images)
+    dev = _require_device(*tensors)
+    L = lib()
+    c = lambda t: t.contiguous() if t is not None else None
+    order_xy, offsets_xy = index_xy if index_xy is not None else (None, None)
+    order_yx, offsets_yx = index_yx if index_yx is not None else (None, None)
+    dx = torch.empty(B, N, 3, dtype=_F32, device=dev) if want_dx else None
+    dy = torch.empty(B, M, 3, dtype=_F32, device=dev) if want_dy else None
+    held = [c(t) for t in (x, y, x_lengths, y_lengths, idx_xy, order_xy, offsets_xy, idx_yx, order_yx, offsets_yx,
+                           grad_points, grad_images)]
+    with torch.cuda.device(dev):
+        rc = L.mr_nearest_backward(*[_ptr(t) for t in held[:4]], B, N, M, *[_ptr(t) for t in held[4:]],
+                                   float(x_weight), float(y_weight), _ptr(dx), _ptr(dy), _stream(dev))
+    _check(rc, "mr_nearest_backward")
+    return dx, dy
 
 
 def _aligned16(t):

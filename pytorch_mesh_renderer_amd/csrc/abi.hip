@@ -841,6 +841,53 @@ int mr_ssim_backward(const float *image, const float *target, const float *saved
                                   dtarget, (hipStream_t)stream);
 }
 
+inline bool bad_nearest_dims(int B, int N, int M) {
+  return B < 1 || B > 65535 || N < 1 || M < 1 || N > (1 << 28) || M > (1 << 28) ||
+         (size_t)B * N >= ((size_t)1 << 36) || (size_t)B * M >= ((size_t)1 << 36);
+}
+
+int mr_nearest_plan(int B, int N, int M, int *splits, int *queries_per_lane, int *target_tile, int *workgroup_size) {
+  if (bad_nearest_dims(B, N, M) || !splits || !queries_per_lane || !target_tile || !workgroup_size) return MR_EINVAL;
+  mr::nearest_plan(B, N, M, splits, queries_per_lane, target_tile, workgroup_size);
+  return MR_OK;
+}
+
+size_t mr_nearest_workspace_bytes(int B, int N, int M) {
+  if (bad_nearest_dims(B, N, M)) return 0;
+  return mr::nearest_ws(B, N, M);
+}
+
+int mr_nearest_forward(const float *x, const float *y, const int32_t *x_lengths, const int32_t *y_lengths, int B, int N,
+                       int M, float *sqdist, int32_t *idx, float *total, float weight, int accumulate, void *workspace,
+                       size_t workspace_bytes, void *stream) {
+  if (bad_nearest_dims(B, N, M)) return MR_EINVAL;
+  if (!x || !y || !idx) return MR_EINVAL;
+  const int rc = check_ws(workspace, workspace_bytes, mr::nearest_ws(B, N, M));
+  if (rc != MR_OK) return rc;
+  return mr::launch_nearest_forward(x, y, x_lengths, y_lengths, B, N, M, sqdist, idx, total, weight, accumulate != 0,
+                                    workspace, (hipStream_t)stream);
+}
+
+int mr_nearest_backward(const float *x, const float *y, const int32_t *x_lengths, const int32_t *y_lengths, int B, int N,
+                        int M, const int32_t *idx_xy, const int32_t *order_xy, const int32_t *offsets_xy,
+                        const int32_t *idx_yx, const int32_t *order_yx, const int32_t *offsets_yx,
+                        const float *grad_points, const float *grad_images, float x_weight, float y_weight, float *dx,
+                        float *dy, void *stream) {
+  if (bad_nearest_dims(B, N, M)) return MR_EINVAL;
+  if (!x || !y) return MR_EINVAL;
+  if (!idx_xy && !idx_yx) return MR_EINVAL;                       // no direction ran
+  if ((grad_points != nullptr) == (grad_images != nullptr)) return MR_EINVAL;   // exactly one upstream
+  if (grad_points && (!idx_xy || idx_yx)) return MR_EINVAL;       // a per-point upstream belongs to x -> y alone
+  if ((order_xy == nullptr) != (offsets_xy == nullptr) || (order_yx == nullptr) != (offsets_yx == nullptr))
+    return MR_EINVAL;
+  // a gradient needs the scatter half of every direction that ran into its cloud
+  if (dx && idx_yx && !order_yx) return MR_EINVAL;
+  if (dy && idx_xy && !order_xy) return MR_EINVAL;
+  return mr::launch_nearest_backward(x, y, x_lengths, y_lengths, B, N, M, idx_xy, order_xy, offsets_xy,
+                                     idx_yx, order_yx, offsets_yx, grad_points, grad_images, x_weight, y_weight, dx, dy,
+                                     (hipStream_t)stream);
+}
+
 int mr_texture_forward(const float *tex, const float *uv, const float *mask, int tex_batched, int Ht, int Wt, int C,
                        int B, int W, int H, int boundary, float *out, void *stream) {
   if (bad_texture_dims(tex_batched, Ht, Wt, C, B, W, H) || bad_boundary(boundary)) return MR_EINVAL;

@@ -258,6 +258,17 @@ int launch_mesh_regularizer_backward(const float *dterms, const float *vertices,
                                      const int32_t *nbr_offsets, const int32_t *nbr, const int32_t *flaps,
                                      const int32_t *role_offsets, const int32_t *roles, int B, int V, int E, int F,
                                      int terms, int use_target, float target, float *dvertices, hipStream_t s);
+// nearest neighbours between point clouds, the Chamfer distance's hot path (nearest.hip)
+void nearest_plan(int B, int N, int M, int *splits, int *queries_per_lane, int *target_tile, int *workgroup);
+size_t nearest_ws(int B, int N, int M);
+int launch_nearest_forward(const float *x, const float *y, const int32_t *x_lengths, const int32_t *y_lengths, int B,
+                           int N, int M, float *sqdist, int32_t *idx, float *total, float weight, int accumulate,
+                           void *ws, hipStream_t s);
+int launch_nearest_backward(const float *x, const float *y, const int32_t *x_lengths, const int32_t *y_lengths, int B,
+                            int N, int M, const int32_t *idx_xy, const int32_t *order_xy, const int32_t *offsets_xy,
+                            const int32_t *idx_yx, const int32_t *order_yx, const int32_t *offsets_yx,
+                            const float *grad_points, const float *grad_images, float x_weight, float y_weight,
+                            float *dx, float *dy, hipStream_t s);
 
 // spherical-harmonics shading (sh_shade.hip)
 size_t sh_shade_backward_ws(int B, int W, int H);

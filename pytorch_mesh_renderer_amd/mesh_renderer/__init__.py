@@ -7,6 +7,7 @@ from .texturing import (attribute_derivatives, render_textured, render_textured_
                         texture_mip_levels)
 from . import losses
 from . import regularizers
+from . import points
 from .graphs import capture_step, CapturedStep
 
 __version__ = '0.0.1'
