@@ -776,6 +776,49 @@ int mr_nearest_backward(const float *x, const float *y, const int32_t *x_lengths
                         const float *grad_points, const float *grad_images, float x_weight, float y_weight, float *dx,
                         float *dy, void *stream);
 
+/* ---- point to nearest triangle: the point-to-mesh distance (no reference counterpart) ----
+ * Per image b, for every query p_i with i < lengths[b], over the T triangles of one shared topology
+ * ("Point-cloud losses"):
+ *   sqdist_i = min_t dist^2(p_i, triangle t)   to the CLOSED triangle: interior, edges and corners
+ *   face_i   = the LOWEST t that attains it (equal float32 distances), whatever the launch shape
+ *   bary_i   = the barycentrics of the closest point c_i = sum_k bary_ik v_k on that triangle, >= 0
+ * dist^2(p, (a, b, c)) with e0 = b - a, e1 = c - a, d = p - a is the least of: the plane projection when
+ * det = |e0|^2 |e1|^2 - (e0.e1)^2 > 0 and its coordinates satisfy v >= 0, w >= 0, v + w <= 1, and the closest points
+ * of the segments ab, bc, ca (parameter clamped to [0, 1]; a zero-length segment is its end point) -- each evaluated
+ * as |d - (beta e0 + gamma e1)|^2, never from an absolute closest point.  A zero-area triangle is its edges or its
+ * point: a finite distance.  A triangle with an index outside [0, V) is never chosen.  A padded query, and a query
+ * for which no triangle compared below +inf (no usable triangle, NaN coordinates), get sqdist 0, face -1, bary 0;
+ * every other face written is a usable triangle's index.
+ *   points [B,N,3], vertices [B,V,3] f32;  triangles [T,3] i32;  lengths [B] i32 (device) or NULL = all N
+ *   sqdist [B,N] f32 out or NULL;  face [B,N] i32 out;  bary [B,N,3] f32 out
+ *   total  [B] f32 out or NULL: the mean of sqdist over image b's valid queries (0 without one), a fixed-order sum
+ * mr_nearest_triangle_plan: the launch shape, a pure host function: the triangles are cut into `splits` runs of
+ * whole `triangle_tile`s, a workgroup of `workgroup_size` threads holds `queries_per_lane` x `workgroup_size` queries;
+ * with splits > 1 the runs meet through 64-bit keys as in mr_nearest_forward.  The workspace holds the per-image
+ * triangle records (80 bytes each), those keys and the partial sums; 16-byte aligned, needed by every call.
+ *
+ * mr_nearest_triangle_backward: the gradient of  sum_i g_i sqdist_i  with the barycentrics held constant (the
+ * envelope theorem):  dpoints_i = 2 g_i (p_i - c_i),  dvertices_k -= 2 g_i bary_ik (p_i - c_i)  for the corners k of
+ * face_i;  g_i = grad_points[b,i] ([B,N]) or grad_images[b] / valid queries ([B], the mean's upstream): exactly one.
+ *   order [B,3N], offsets [B,V+1] i32: the inverted index of the entries 3 i + k keyed by the vertex
+ *         triangles[face_i][k] (-1 for rows without a face), each vertex's entries in a FIXED order (a stable sort,
+ *         as for mr_nearest_backward); needed when dvertices is asked for
+ *   dpoints [B,N,3], dvertices [B,V,3] f32 out or NULL (not computed); each is written completely
+ * No atomics, no zero-fills, bit-reproducible in either deterministic mode.
+ * 1 <= B <= 65535, 1 <= N, V, T <= 2^28, B * N, B * V and B * T below 2^36; sizes outside are MR_EINVAL (queries
+ * return 0). */
+int mr_nearest_triangle_plan(int B, int N, int T, int *splits, int *queries_per_lane, int *triangle_tile,
+                             int *workgroup_size);
+size_t mr_nearest_triangle_workspace_bytes(int B, int N, int T);
+int mr_nearest_triangle_forward(const float *points, const float *vertices, const int32_t *triangles,
+                                const int32_t *lengths, int B, int N, int V, int T, float *sqdist, int32_t *face,
+                                float *bary, float *total, void *workspace, size_t workspace_bytes, void *stream);
+int mr_nearest_triangle_backward(const float *points, const float *vertices, const int32_t *triangles,
+                                 const int32_t *lengths, int B, int N, int V, int T, const int32_t *face,
+                                 const float *bary, const int32_t *order, const int32_t *offsets,
+                                 const float *grad_points, const float *grad_images, float *dpoints, float *dvertices,
+                                 void *stream);
+
 /* ---- clip-space transforms --------------------------------------------------------------
  * perspective(aspect, fov_y, near, far) . look_at(eye, center, up) per image, the product render() and
  * rasterize() apply to the vertices (src/common/camera_utils.py:45-139; src/mesh_renderer/render.py

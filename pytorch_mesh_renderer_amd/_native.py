@@ -344,6 +344,18 @@ def lib():
         except AttributeError as e:   # the point-cloud entry points came without an ABI version bump
             raise NativeLibraryError("%s lacks the nearest-neighbour entry points (%s): rebuild it (make -C "
                                      "pytorch_mesh_renderer_amd/csrc)" % (LIB_PATH, e))
+        try:
+            L.mr_nearest_triangle_plan.argtypes = [ci] * 3 + [vp] * 4
+            L.mr_nearest_triangle_plan.restype = ci
+            L.mr_nearest_triangle_workspace_bytes.argtypes = [ci] * 3
+            L.mr_nearest_triangle_workspace_bytes.restype = sz
+            L.mr_nearest_triangle_forward.argtypes = [vp] * 4 + [ci] * 4 + [vp] * 5 + [sz, vp]
+            L.mr_nearest_triangle_forward.restype = ci
+            L.mr_nearest_triangle_backward.argtypes = [vp] * 4 + [ci] * 4 + [vp] * 9
+            L.mr_nearest_triangle_backward.restype = ci
+        except AttributeError as e:   # the point-to-mesh entry points came without an ABI version bump
+            raise NativeLibraryError("%s lacks the nearest-triangle entry points (%s): rebuild it (make -C "
+                                     "pytorch_mesh_renderer_amd/csrc)" % (LIB_PATH, e))
         _lib = L
     return _lib
 
@@ -1098,6 +1110,87 @@ def nearest_backward(x, y, x_lengths, y_lengths, idx_xy=None, index_xy=None, idx
                                    float(x_weight), float(y_weight), _ptr(dx), _ptr(dy), _stream(dev))
     _check(rc, "mr_nearest_backward")
     return dx, dy
+
+
+def nearest_triangle_plan(B, N, T):
+    """The launch shape mr_nearest_triangle_forward takes for B images of N queries against T triangles, a pure host
+    function: {"splits", "queries_per_lane", "triangle_tile", "workgroup_size"} (include/mesh_raster.h)."""
+    out = (ctypes.c_int * 4)()
+    rc = lib().mr_nearest_triangle_plan(int(B), int(N), int(T),
+                                        *[ctypes.c_void_p(ctypes.addressof(out) + 4 * k) for k in range(4)])
+    if rc != MR_OK:
+        raise ValueError("nearest_triangle_plan takes 1..65535 images of 1..2^28 points and triangles, got (%r, %r, %r)"
+                         % (B, N, T))
+    return dict(zip(("splits", "queries_per_lane", "triangle_tile", "workgroup_size"), list(out)))
+
+
+def _chk_point_mesh(points, vertices, triangles, lengths):
+    _chk("points", points, _F32, None, None, 3)
+    B, N, _ = points.shape
+    _chk("vertices", vertices, _F32, B, None, 3)
+    V = vertices.shape[1]
+    _chk("triangles", triangles, _I32, None, 3)
+    T = triangles.shape[0]
+    if (not 1 <= B <= 65535 or not all(1 <= n <= 1 << 28 and B * n < 1 << 36 for n in (N, V, T))):
+        raise ValueError("the point-to-mesh kernels take 1..65535 images of 1..2^28 points, vertices and triangles, "
+                         "got %s, %s and %s" % (list(points.shape), list(vertices.shape), list(triangles.shape)))
+    if lengths is not None:
+        _chk("lengths", lengths, _I32, B)
+    return B, N, V, T
+
+
+def nearest_triangle_forward(points, vertices, triangles, lengths=None, want_sqdist=True, want_total=False):
+    """points [B,N,3], vertices [B,V,3] f32, triangles [T,3] i32, lengths [B] i32 or None (device) -> (sqdist [B,N]
+    f32 or None, face [B,N] i32, bary [B,N,3] f32, total [B] f32 or None: the mean of sqdist over each image's valid
+    queries): mr_nearest_triangle_forward."""
+    B, N, V, T = _chk_point_mesh(points, vertices, triangles, lengths)
+    dev = _require_device(points, vertices, triangles, *([lengths] if lengths is not None else []))
+    L = lib()
+    points, vertices, triangles = points.contiguous(), vertices.contiguous(), triangles.contiguous()
+    lengths = lengths.contiguous() if lengths is not None else None
+    sqdist = torch.empty(B, N, dtype=_F32, device=dev) if want_sqdist else None
+    face = torch.empty(B, N, dtype=_I32, device=dev)
+    bary = torch.empty(B, N, 3, dtype=_F32, device=dev)
+    total = torch.empty(B, dtype=_F32, device=dev) if want_total else None
+    with torch.cuda.device(dev):
+        ws, have = _workspace(dev, L.mr_nearest_triangle_workspace_bytes(B, N, T))
+        rc = L.mr_nearest_triangle_forward(_ptr(points), _ptr(vertices), _ptr(triangles), _ptr(lengths), B, N, V, T,
+                                           _ptr(sqdist), _ptr(face), _ptr(bary), _ptr(total), _ptr(ws), have,
+                                           _stream(dev))
+    _check(rc, "mr_nearest_triangle_forward")
+    return sqdist, face, bary, total
+
+
+def nearest_triangle_backward(points, vertices, triangles, lengths, face, bary, index=None, grad_points=None,
+                              grad_images=None, want_dpoints=True, want_dvertices=True):
+    """mr_nearest_triangle_backward -> (dpoints [B,N,3] or None, dvertices [B,V,3] or None).  index: (order [B,3N],
+    offsets [B,V+1]), nearest_inverted_index() of the (query, corner) entries' vertices, needed for dvertices."""
+    B, N, V, T = _chk_point_mesh(points, vertices, triangles, lengths)
+    _chk("face", face, _I32, B, N)
+    _chk("bary", bary, _F32, B, N, 3)
+    tensors = [points, vertices, triangles, face, bary] + ([lengths] if lengths is not None else [])
+    if index is not None:
+        _chk("order", index[0], _I32, B, 3 * N)
+        _chk("offsets", index[1], _I32, B, V + 1)
+        tensors += list(index)
+    if grad_points is not None:
+        _chk("upstream gradient", grad_points, _F32, B, N)
+        tensors.append(grad_points)
+    if grad_images is not None:
+        _chk("upstream gradient", grad_images, _F32, B)
+        tensors.append(grad_images)
+    dev = _require_device(*tensors)
+    L = lib()
+    c = lambda t: t.contiguous() if t is not None else None
+    order, offsets = index if index is not None else (None, None)
+    dpoints = torch.empty(B, N, 3, dtype=_F32, device=dev) if want_dpoints else None
+    dvertices = torch.empty(B, V, 3, dtype=_F32, device=dev) if want_dvertices else None
+    held = [c(t) for t in (points, vertices, triangles, lengths, face, bary, order, offsets, grad_points, grad_images)]
+    with torch.cuda.device(dev):
+        rc = L.mr_nearest_triangle_backward(*[_ptr(t) for t in held[:4]], B, N, V, T, *[_ptr(t) for t in held[4:]],
+                                            _ptr(dpoints), _ptr(dvertices), _stream(dev))
+    _check(rc, "mr_nearest_triangle_backward")
+    return dpoints, dvertices
 
 
 def _aligned16(t):

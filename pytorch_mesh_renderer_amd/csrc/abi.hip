@@ -888,6 +888,49 @@ int mr_nearest_backward(const float *x, const float *y, const int32_t *x_lengths
                                      (hipStream_t)stream);
 }
 
+inline bool bad_nearest_triangle_dims(int B, int N, int V, int T) {
+  return bad_nearest_dims(B, N, T) || V < 1 || V > (1 << 28) || (size_t)B * V >= ((size_t)1 << 36);
+}
+
+int mr_nearest_triangle_plan(int B, int N, int T, int *splits, int *queries_per_lane, int *triangle_tile,
+                             int *workgroup_size) {
+  if (bad_nearest_dims(B, N, T) || !splits || !queries_per_lane || !triangle_tile || !workgroup_size) return MR_EINVAL;
+  mr::nearest_triangle_plan(B, N, T, splits, queries_per_lane, triangle_tile, workgroup_size);
+  return MR_OK;
+}
+
+size_t mr_nearest_triangle_workspace_bytes(int B, int N, int T) {
+  if (bad_nearest_dims(B, N, T)) return 0;
+  return mr::nearest_triangle_ws(B, N, T);
+}
+
+int mr_nearest_triangle_forward(const float *points, const float *vertices, const int32_t *triangles,
+                                const int32_t *lengths, int B, int N, int V, int T, float *sqdist, int32_t *face,
+                                float *bary, float *total, void *workspace, size_t workspace_bytes, void *stream) {
+  if (bad_nearest_triangle_dims(B, N, V, T)) return MR_EINVAL;
+  if (!points || !vertices || !triangles || !face || !bary) return MR_EINVAL;
+  const int rc = check_ws(workspace, workspace_bytes, mr::nearest_triangle_ws(B, N, T));
+  if (rc != MR_OK) return rc;
+  if (misaligned(workspace, 16)) return MR_EINVAL;   // the records are read as 16-byte words
+  return mr::launch_nearest_triangle_forward(points, vertices, triangles, lengths, B, N, V, T, sqdist, face, bary, total,
+                                             workspace, (hipStream_t)stream);
+}
+
+int mr_nearest_triangle_backward(const float *points, const float *vertices, const int32_t *triangles,
+                                 const int32_t *lengths, int B, int N, int V, int T, const int32_t *face,
+                                 const float *bary, const int32_t *order, const int32_t *offsets,
+                                 const float *grad_points, const float *grad_images, float *dpoints, float *dvertices,
+                                 void *stream) {
+  if (bad_nearest_triangle_dims(B, N, V, T)) return MR_EINVAL;
+  if (!points || !vertices || !triangles || !face || !bary) return MR_EINVAL;
+  if ((grad_points != nullptr) == (grad_images != nullptr)) return MR_EINVAL;   // exactly one upstream
+  if ((order == nullptr) != (offsets == nullptr)) return MR_EINVAL;
+  if (dvertices && !order) return MR_EINVAL;                      // the vertices' gradient is a gather over the index
+  return mr::launch_nearest_triangle_backward(points, vertices, triangles, lengths, B, N, V, T, face, bary, order,
+                                              offsets, grad_points, grad_images, dpoints, dvertices,
+                                              (hipStream_t)stream);
+}
+
 int mr_texture_forward(const float *tex, const float *uv, const float *mask, int tex_batched, int Ht, int Wt, int C,
                        int B, int W, int H, int boundary, float *out, void *stream) {
   if (bad_texture_dims(tex_batched, Ht, Wt, C, B, W, H) || bad_boundary(boundary)) return MR_EINVAL;

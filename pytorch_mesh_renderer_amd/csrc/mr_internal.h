@@ -269,6 +269,17 @@ int launch_nearest_backward(const float *x, const float *y, const int32_t *x_len
                             const int32_t *idx_yx, const int32_t *order_yx, const int32_t *offsets_yx,
                             const float *grad_points, const float *grad_images, float x_weight, float y_weight,
                             float *dx, float *dy, hipStream_t s);
+// point to nearest triangle, mr_nearest_triangle_* (nearest.hip)
+void nearest_triangle_plan(int B, int N, int T, int *splits, int *queries_per_lane, int *triangle_tile, int *workgroup);
+size_t nearest_triangle_ws(int B, int N, int T);
+int launch_nearest_triangle_forward(const float *points, const float *vertices, const int32_t *triangles,
+                                    const int32_t *lengths, int B, int N, int V, int T, float *sqdist, int32_t *face,
+                                    float *bary, float *total, void *ws, hipStream_t s);
+int launch_nearest_triangle_backward(const float *points, const float *vertices, const int32_t *triangles,
+                                     const int32_t *lengths, int B, int N, int V, int T, const int32_t *face,
+                                     const float *bary, const int32_t *order, const int32_t *offsets,
+                                     const float *grad_points, const float *grad_images, float *dpoints,
+                                     float *dvertices, hipStream_t s);
 
 // spherical-harmonics shading (sh_shade.hip)
 size_t sh_shade_backward_ws(int B, int W, int H);

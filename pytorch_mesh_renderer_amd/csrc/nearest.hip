@@ -1,5 +1,6 @@
 // Brute-force nearest neighbour between two point clouds on gfx950, the hot path of the Chamfer distance
-// (mr_nearest_forward / _backward; semantics: INTEGRATION.md, "Point-cloud losses").
+// (mr_nearest_forward / _backward; semantics: INTEGRATION.md, "Point-cloud losses"), and further down the same search
+// from points to the triangles of a mesh (mr_nearest_triangle_forward / _backward: "point to triangle").
 //
 // Per image b, for every query x_i (i < x_lengths[b]) over the targets y_j (j < y_lengths[b]):
 //   sqdist_i = min_j (x_i - y_j).(x_i - y_j),   idx_i = the lowest j that attains it
@@ -46,19 +47,21 @@ struct Plan {
   int splits, queries_per_lane, query_blocks, chunk;   // chunk: targets per split, whole tiles
 };
 
-inline Plan plan_of(int B, int N, int M) {
+// M targets in tiles of `tile`, `wide` queries a lane once a cloud fills a workgroup of them: the point search's
+// shape by default, the triangle search's with its own two constants
+inline Plan plan_of(int B, int N, int M, int tile = kTile, int wide = kWideQueries) {
   Plan p;
-  p.queries_per_lane = N >= kThreads * kWideQueries ? kWideQueries : 1;
+  p.queries_per_lane = N >= kThreads * wide ? wide : 1;
   const int per_block = kThreads * p.queries_per_lane;
   p.query_blocks = (N + per_block - 1) / per_block;
-  const int tiles = (M + kTile - 1) / kTile;
+  const int tiles = (M + tile - 1) / tile;
   const long long blocks = (long long)B * p.query_blocks;
   long long want = (kFillBlocks + blocks - 1) / blocks;
   if (want < 1) want = 1;
   int splits = (int)(want < tiles ? want : tiles);
   const int chunk_tiles = (tiles + splits - 1) / splits;
   p.splits = (tiles + chunk_tiles - 1) / chunk_tiles;   // no split without a tile
-  p.chunk = chunk_tiles * kTile;
+  p.chunk = chunk_tiles * tile;
   return p;
 }
 
@@ -315,6 +318,324 @@ __global__ __launch_bounds__(kThreads) void k_nearest_backward(
   if (have && sub == 0) dp[(size_t)b * Np + p] = V3{dx, dy, dz};
 }
 
+// ---- point to triangle ------------------------------------------------------------------------------------------
+// mr_nearest_triangle_forward / _backward: per image, for every query p_i the squared distance to the nearest CLOSED
+// triangle of one shared topology, the lowest face that attains it and the barycentrics of the closest point
+// ("Point-cloud losses").  dist^2(p, (a, b, c)) is the least of up to four candidates -- the plane
+// projection where it falls inside (det > 0, v >= 0, w >= 0, v + w <= 1) and the closest points of the segments ab,
+// bc and ca (parameter clamped to [0, 1], a zero-length segment is its end point) -- each evaluated in the
+// difference form relative to the first corner, |d - (beta e0 + gamma e1)|^2 with d = p - a.  A zero-area triangle is
+// therefore its edges or its point: finite, never NaN.
+//
+// k_nt_setup gathers every image's triangles into 80-byte records (a, e0, e1, e2 = c - b, the three dot products
+// and four reciprocals, formed in float64 from the float32 edges); a triangle with an index outside [0, V) becomes
+// a record with a = +inf, whose every distance is +inf or NaN and never compares below the running best.  k_nt_search
+// is k_nearest over those records: 128 of them staged in LDS, every lane reading the same record as four
+// ds_read_b128 and a ds_read_b96 (a broadcast), one or two queries a lane -- two in packed fp32 -- ascending faces and a strict '<',
+// 64-bit keys and k_nearest_merge when the faces are split.  It keeps the distance and the face only.  k_nt_finish
+// evaluates the chosen face again with the SAME device functions (tri_candidates / tri_distance, compiled without
+// contraction and with explicit fused multiply-adds, so that the scalar and the packed instantiation round alike):
+// the distance it writes is the one that won, bit for bit.  The mean is k_nearest_mean over its partial sums.
+//
+// Backward (the envelope theorem: the barycentrics are constants): dp_i = 2 g_i (p_i - c_i), one row per query, and
+// dv_k = -sum 2 g_i bary_ik (p_i - c_i) as a gather over the inverted index of the 3N (query, corner) entries keyed
+// by vertex, eight lanes per vertex and the butterfly of k_nearest_backward; p - c is d - (beta e0 + gamma e1) again.
+constexpr int kTriTile = 128;          // records staged in LDS at a time (10 KB), and the granularity of a split
+constexpr int kTriWideQueries = 2;     // queries per lane once a cloud fills a workgroup of them: one packed pair
+constexpr int kRecWords = 5;           // 16-byte words per record
+// word 0: a.xyz, 1 / det (0 unless det > 0)      word 1: e0.xyz, 1 / |e0|^2 (0 for a zero-length edge)
+// word 2: e1.xyz, 1 / |e1|^2                      word 3: e2.xyz, 1 / |e2|^2         word 4: |e0|^2, e0.e1, |e1|^2, -
+
+__device__ __forceinline__ float fma_of(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+__device__ __forceinline__ F2 fma_of(F2 a, F2 b, F2 c) { return __builtin_elementwise_fma(a, b, c); }
+__device__ __forceinline__ float clamp01(float t) { return fmaxf(fminf(t, 1.0f), 0.0f); }
+__device__ __forceinline__ F2 clamp01(F2 t) { return F2{clamp01(t.x), clamp01(t.y)}; }
+__device__ __forceinline__ bool inside_of(float v, float w) { return v >= 0.0f && w >= 0.0f && v + w <= 1.0f; }
+__device__ __forceinline__ float where_inside(float v, float w, float d) { return inside_of(v, w) ? d : INFINITY; }
+__device__ __forceinline__ F2 where_inside(F2 v, F2 w, F2 d) {
+  return F2{where_inside(v.x, w.x, d.x), where_inside(v.y, w.y, d.y)};
+}
+__device__ __forceinline__ float lesser(float a, float b) { return a < b ? a : b; }   // b when a is NaN
+__device__ __forceinline__ F2 lesser(F2 a, F2 b) { return F2{lesser(a.x, b.x), lesser(a.y, b.y)}; }
+__device__ __forceinline__ float part_of(float v, int) { return v; }
+__device__ __forceinline__ float part_of(F2 v, int q) { return q == 0 ? v.x : v.y; }
+
+// The four candidates of one triangle for one (float) or two (F2) queries: squared distances and parameters.
+template <typename F>
+struct Candidates {
+  F inside, ab, bc, ca;   // squared distances; `inside` is +inf where the projection is no candidate
+  F v, w, tab, tbc, tca;
+};
+
+template <typename F>
+__device__ __forceinline__ Candidates<F> tri_candidates(F px, F py, F pz, float4 r0, float4 r1, float4 r2, float4 r3,
+                                                        float4 r4) {
+#pragma clang fp contract(off)   // every fused multiply-add below is spelled: both instantiations round alike
+  Candidates<F> c;
+  const F dx = px - (F)r0.x, dy = py - (F)r0.y, dz = pz - (F)r0.z;
+  const F p0 = fma_of(dz, (F)r1.z, fma_of(dy, (F)r1.y, dx * (F)r1.x));
+  const F p1 = fma_of(dz, (F)r2.z, fma_of(dy, (F)r2.y, dx * (F)r2.x));
+  {   // segment ab: a + t e0
+    c.tab = clamp01(p0 * (F)r1.w);
+    const F x = fma_of(c.tab, (F)-r1.x, dx), y = fma_of(c.tab, (F)-r1.y, dy), z = fma_of(c.tab, (F)-r1.z, dz);
+    c.ab = fma_of(z, z, fma_of(y, y, x * x));
+  }
+  {   // segment ca, walked from a: a + t e1
+    c.tca = clamp01(p1 * (F)r2.w);
+    const F x = fma_of(c.tca, (F)-r2.x, dx), y = fma_of(c.tca, (F)-r2.y, dy), z = fma_of(c.tca, (F)-r2.z, dz);
+    c.ca = fma_of(z, z, fma_of(y, y, x * x));
+  }
+  {   // segment bc: a + e0 + t e2
+    const F bx = dx - (F)r1.x, by = dy - (F)r1.y, bz = dz - (F)r1.z;
+    c.tbc = clamp01(fma_of(bz, (F)r3.z, fma_of(by, (F)r3.y, bx * (F)r3.x)) * (F)r3.w);
+    const F x = fma_of(c.tbc, (F)-r3.x, bx), y = fma_of(c.tbc, (F)-r3.y, by), z = fma_of(c.tbc, (F)-r3.z, bz);
+    c.bc = fma_of(z, z, fma_of(y, y, x * x));
+  }
+  {   // the plane projection a + v e0 + w e1
+    c.v = fma_of(p0, (F)r4.z, -(p1 * (F)r4.y)) * (F)r0.w;
+    c.w = fma_of(p1, (F)r4.x, -(p0 * (F)r4.y)) * (F)r0.w;
+    const F x = fma_of(c.w, (F)-r2.x, fma_of(c.v, (F)-r1.x, dx));
+    const F y = fma_of(c.w, (F)-r2.y, fma_of(c.v, (F)-r1.y, dy));
+    const F z = fma_of(c.w, (F)-r2.z, fma_of(c.v, (F)-r1.z, dz));
+    const F d = fma_of(z, z, fma_of(y, y, x * x));
+    c.inside = r0.w > 0.0f ? where_inside(c.v, c.w, d) : (F)INFINITY;   // (r0.w: the same on every lane)
+  }
+  return c;
+}
+
+// The nearest candidate: +inf when none compares below it (NaN candidates are passed over).
+template <typename F>
+__device__ __forceinline__ F tri_distance(const Candidates<F> &c) {
+  return lesser(c.ca, lesser(c.bc, lesser(c.ab, lesser(c.inside, (F)INFINITY))));
+}
+
+// grid (ceil(T / kThreads), B): records [B, T, kRecWords] of 16-byte words
+__global__ __launch_bounds__(kThreads) void k_nt_setup(const V3 *__restrict__ vertices,
+                                                       const int32_t *__restrict__ triangles, int V, int T,
+                                                       float4 *__restrict__ records) {
+  const int b = (int)blockIdx.y, t = (int)blockIdx.x * kThreads + (int)threadIdx.x;
+  if (t >= T) return;
+  float4 *out = records + ((size_t)b * T + t) * kRecWords;
+  const int ia = triangles[3 * (size_t)t], ib = triangles[3 * (size_t)t + 1], ic = triangles[3 * (size_t)t + 2];
+  const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  if ((unsigned)ia >= (unsigned)V || (unsigned)ib >= (unsigned)V || (unsigned)ic >= (unsigned)V) {
+    out[0] = make_float4(INFINITY, INFINITY, INFINITY, 0.0f);   // d = p - a is -inf or NaN: never below the best
+    out[1] = out[2] = out[3] = out[4] = zero;
+    return;
+  }
+  const V3 *vb = vertices + (size_t)b * V;
+  const V3 a = vb[ia], p = vb[ib], c = vb[ic];
+  const float e0x = p.x - a.x, e0y = p.y - a.y, e0z = p.z - a.z;
+  const float e1x = c.x - a.x, e1y = c.y - a.y, e1z = c.z - a.z;
+  const float e2x = c.x - p.x, e2y = c.y - p.y, e2z = c.z - p.z;
+  const double d00 = (double)e0x * e0x + (double)e0y * e0y + (double)e0z * e0z;
+  const double d01 = (double)e0x * e1x + (double)e0y * e1y + (double)e0z * e1z;
+  const double d11 = (double)e1x * e1x + (double)e1y * e1y + (double)e1z * e1z;
+  const double d22 = (double)e2x * e2x + (double)e2y * e2y + (double)e2z * e2z;
+  const double det = d00 * d11 - d01 * d01;
+  out[0] = make_float4(a.x, a.y, a.z, det > 0.0 ? (float)(1.0 / det) : 0.0f);
+  out[1] = make_float4(e0x, e0y, e0z, d00 > 0.0 ? (float)(1.0 / d00) : 0.0f);
+  out[2] = make_float4(e1x, e1y, e1z, d11 > 0.0 ? (float)(1.0 / d11) : 0.0f);
+  out[3] = make_float4(e2x, e2y, e2z, d22 > 0.0 ? (float)(1.0 / d22) : 0.0f);
+  out[4] = make_float4((float)d00, (float)d01, (float)d11, 0.0f);
+}
+
+// grid (query blocks, splits, B).  keys != null (splits > 1): one key per (image, split, query) for k_nearest_merge;
+// keys == null: the face, -1 for a padded query and for one no triangle compared below +inf for.
+template <typename F>
+__global__ __launch_bounds__(kThreads) void k_nt_search(const float *__restrict__ points,
+                                                        const float4 *__restrict__ records,
+                                                        const int32_t *__restrict__ lengths, int N, int T, int chunk,
+                                                        int32_t *__restrict__ face,
+                                                        unsigned long long *__restrict__ keys) {
+  constexpr int Q = (int)(sizeof(F) / sizeof(float));
+  __shared__ float4 tile[kTriTile * kRecWords];
+  const int b = (int)blockIdx.z, split = (int)blockIdx.y;
+  const int nv = valid_count(lengths, b, N);
+  const float *pb = points + (size_t)b * N * 3;
+  const float4 *rb = records + (size_t)b * T * kRecWords;
+  const int j0 = min(split * chunk, T), j1 = min(j0 + chunk, T);
+  const int i0 = (int)blockIdx.x * (kThreads * Q) + (int)threadIdx.x;
+
+  float p[3][Q], best[Q];
+  int bi[Q];
+#pragma unroll
+  for (int q = 0; q < Q; ++q) {
+    const int i = i0 + q * kThreads;
+    const bool have = i < nv;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) p[c][q] = have ? pb[3 * (size_t)i + c] : 0.0f;
+    best[q] = INFINITY;
+    bi[q] = -1;
+  }
+  F px, py, pz;
+  if constexpr (Q == 2) {
+    px = F{p[0][0], p[0][1]};
+    py = F{p[1][0], p[1][1]};
+    pz = F{p[2][0], p[2][1]};
+  } else {
+    px = p[0][0];
+    py = p[1][0];
+    pz = p[2][0];
+  }
+
+  for (int t0 = j0; t0 < j1; t0 += kTriTile) {   // j0, j1: the same on every thread
+    const int count = min(kTriTile, j1 - t0);
+    __syncthreads();
+    for (int f = (int)threadIdx.x; f < count * kRecWords; f += kThreads) tile[f] = rb[(size_t)t0 * kRecWords + f];
+    __syncthreads();
+    for (int j = 0; j < count; ++j) {
+      const float4 *r = &tile[j * kRecWords];   // one address for the wavefront
+      const F d = tri_distance(tri_candidates<F>(px, py, pz, r[0], r[1], r[2], r[3], r[4]));
+#pragma unroll
+      for (int q = 0; q < Q; ++q) {
+        const float dq = part_of(d, q);
+        if (dq < best[q]) {   // strict, faces ascending: the lowest face of equal distances; NaN and +inf never win
+          best[q] = dq;
+          bi[q] = t0 + j;
+        }
+      }
+    }
+  }
+
+#pragma unroll
+  for (int q = 0; q < Q; ++q) {
+    const int i = i0 + q * kThreads;
+    if (i >= N) continue;
+    const bool found = i < nv && bi[q] >= 0;
+    if (keys)
+      keys[((size_t)b * gridDim.y + split) * N + i] =
+          found ? ((unsigned long long)__float_as_uint(best[q]) << 32) | (unsigned)bi[q] : kNoKey;
+    else
+      face[(size_t)b * N + i] = found ? bi[q] : -1;
+  }
+}
+
+// The chosen face once more, with the search's own functions -> sqdist, the face (-1 for a row without a result),
+// the barycentrics and the workgroup's partial sum.  grid (ceil(N / kThreads), B)
+__global__ __launch_bounds__(kThreads) void k_nt_finish(const V3 *__restrict__ points,
+                                                        const float4 *__restrict__ records,
+                                                        const int32_t *__restrict__ lengths, int N, int T,
+                                                        float *__restrict__ sqdist, int32_t *__restrict__ face,
+                                                        V3 *__restrict__ bary, float *__restrict__ partials) {
+  const int b = (int)blockIdx.y;
+  const int i = (int)blockIdx.x * kThreads + (int)threadIdx.x;
+  const int nv = valid_count(lengths, b, N);
+  float d = 0.0f;
+  if (i < N) {
+    const size_t row = (size_t)b * N + i;
+    int f = i < nv ? face[row] : -1;
+    V3 w = {0.0f, 0.0f, 0.0f};
+    if ((unsigned)f < (unsigned)T) {
+      const V3 p = points[row];
+      const float4 *r = records + ((size_t)b * T + f) * kRecWords;
+      const Candidates<float> c = tri_candidates<float>(p.x, p.y, p.z, r[0], r[1], r[2], r[3], r[4]);
+      d = tri_distance(c);
+      // the same chain as tri_distance, remembering whose parameters won
+      float best = INFINITY, beta = 0.0f, gamma = 0.0f;
+      if (c.inside < best) best = c.inside, beta = c.v, gamma = c.w;
+      if (c.ab < best) best = c.ab, beta = c.tab, gamma = 0.0f;
+      if (c.bc < best) best = c.bc, beta = 1.0f - c.tbc, gamma = c.tbc;
+      if (c.ca < best) best = c.ca, beta = 0.0f, gamma = c.tca;
+      w = V3{fmaxf(1.0f - (beta + gamma), 0.0f), beta, gamma};
+      if (!(d < INFINITY)) f = -1;   // (the search never names such a face)
+    } else {
+      f = -1;
+    }
+    if (f < 0) {
+      d = 0.0f;
+      w = V3{0.0f, 0.0f, 0.0f};
+    }
+    if (sqdist) sqdist[row] = d;
+    face[row] = f;
+    bary[row] = w;
+  }
+  if (partials) {   // (a kernel argument: the same on every thread)
+    d = block_sum(d);
+    if (threadIdx.x == 0) partials[(size_t)b * gridDim.x + blockIdx.x] = d;
+  }
+}
+
+// p_i - c_i = d - (beta e0 + gamma e1) of query i and its weights; false for a row without a face.
+__device__ __forceinline__ bool nt_residual(const V3 *__restrict__ pb, const V3 *__restrict__ vb,
+                                            const int32_t *__restrict__ triangles, const int32_t *__restrict__ fb,
+                                            const V3 *__restrict__ wb, int i, int V, int T, V3 &r, V3 &w) {
+  const int f = fb[i];
+  if ((unsigned)f >= (unsigned)T) return false;
+  const int ia = triangles[3 * (size_t)f], ib = triangles[3 * (size_t)f + 1], ic = triangles[3 * (size_t)f + 2];
+  if ((unsigned)ia >= (unsigned)V || (unsigned)ib >= (unsigned)V || (unsigned)ic >= (unsigned)V) return false;
+  const V3 p = pb[i], a = vb[ia], e = vb[ib], c = vb[ic];
+  w = wb[i];
+  r.x = (p.x - a.x) - (w.y * (e.x - a.x) + w.z * (c.x - a.x));
+  r.y = (p.y - a.y) - (w.y * (e.y - a.y) + w.z * (c.y - a.y));
+  r.z = (p.z - a.z) - (w.y * (e.z - a.z) + w.z * (c.z - a.z));
+  return true;
+}
+
+// dpoints[b, i] = 2 g_i (p_i - c_i), 0 for a row without a face.  grid (ceil(N / kThreads), B)
+__global__ __launch_bounds__(kThreads) void k_nt_backward_points(
+    const V3 *__restrict__ points, const V3 *__restrict__ vertices, const int32_t *__restrict__ triangles,
+    const int32_t *__restrict__ lengths, int N, int V, int T, const int32_t *__restrict__ face,
+    const V3 *__restrict__ bary, const float *__restrict__ g_points, const float *__restrict__ g_images,
+    V3 *__restrict__ dpoints) {
+  const int b = (int)blockIdx.y;
+  const int i = (int)blockIdx.x * kThreads + (int)threadIdx.x;
+  if (i >= N) return;
+  const int nv = valid_count(lengths, b, N);
+  const Upstream up{g_points, (g_images && nv > 0) ? g_images[b] / (float)nv : 0.0f};
+  V3 out = {0.0f, 0.0f, 0.0f}, r, w;
+  if (i < nv && nt_residual(points + (size_t)b * N, vertices + (size_t)b * V, triangles, face + (size_t)b * N,
+                            bary + (size_t)b * N, i, V, T, r, w)) {
+    const float g2 = 2.0f * up.at((size_t)b * N + i);
+    out = V3{g2 * r.x, g2 * r.y, g2 * r.z};
+  }
+  dpoints[(size_t)b * N + i] = out;
+}
+
+// dvertices[b, v] = -sum over the (query, corner) entries that name v of 2 g_i bary_ik (p_i - c_i): order [B, 3N]
+// holds the entries 3 i + k grouped by vertex, each group ascending, offsets [B, V + 1].  Eight lanes per vertex.
+// grid (ceil(V / kPointsPerBlock), B)
+__global__ __launch_bounds__(kThreads) void k_nt_backward_vertices(
+    const V3 *__restrict__ points, const V3 *__restrict__ vertices, const int32_t *__restrict__ triangles,
+    const int32_t *__restrict__ lengths, int N, int V, int T, const int32_t *__restrict__ face,
+    const V3 *__restrict__ bary, const int32_t *__restrict__ order, const int32_t *__restrict__ offsets,
+    const float *__restrict__ g_points, const float *__restrict__ g_images, V3 *__restrict__ dvertices) {
+  const int b = (int)blockIdx.y;
+  const int v = (int)blockIdx.x * kPointsPerBlock + (int)threadIdx.x / kLanesPerPoint;
+  const int sub = (int)threadIdx.x % kLanesPerPoint;
+  const bool have = v < V;   // (whole groups of eight: the butterfly below stays inside one)
+  const int nv = valid_count(lengths, b, N);
+  const Upstream up{g_points, (g_images && nv > 0) ? g_images[b] / (float)nv : 0.0f};
+  float dx = 0.0f, dy = 0.0f, dz = 0.0f;
+  if (have) {
+    const int32_t *off = offsets + (size_t)b * (V + 1);
+    const int e0 = max(off[v], 0), e1 = min(off[v + 1], 3 * N);
+    for (int k = e0 + sub; k < e1; k += kLanesPerPoint) {
+      const int e = order[(size_t)b * 3 * N + k];
+      if ((unsigned)e >= (unsigned)(3 * N)) continue;
+      const int i = e / 3, corner = e - 3 * i;
+      V3 r, w;
+      if (i >= nv || !nt_residual(points + (size_t)b * N, vertices + (size_t)b * V, triangles, face + (size_t)b * N,
+                                  bary + (size_t)b * N, i, V, T, r, w))
+        continue;
+      const float s = -2.0f * up.at((size_t)b * N + i) * (corner == 0 ? w.x : (corner == 1 ? w.y : w.z));
+      dx += s * r.x;
+      dy += s * r.y;
+      dz += s * r.z;
+    }
+  }
+#pragma unroll
+  for (int m = 1; m < kLanesPerPoint; m <<= 1) {
+    dx += __shfl_xor(dx, m, kLanesPerPoint);
+    dy += __shfl_xor(dy, m, kLanesPerPoint);
+    dz += __shfl_xor(dz, m, kLanesPerPoint);
+  }
+  if (have && sub == 0) dvertices[(size_t)b * V + v] = V3{dx, dy, dz};
+}
+
+inline Plan tri_plan_of(int B, int N, int T) { return plan_of(B, N, T, kTriTile, kTriWideQueries); }
+inline size_t tri_records_bytes(int B, int T) { return align_up((size_t)B * T * kRecWords * sizeof(float4), 256); }
+
 }  // namespace
 
 void nearest_plan(int B, int N, int M, int *splits, int *queries_per_lane, int *target_tile, int *workgroup) {
@@ -378,6 +699,82 @@ int launch_nearest_backward(const float *x, const float *y, const int32_t *x_len
     hipLaunchKernelGGL(k_nearest_backward, grid, dim3(kThreads), 0, s, (const V3 *)y, (const V3 *)x, y_lengths,
                        x_lengths, M, N, idx_yx, (const float *)nullptr, y_weight, order_xy, offsets_xy, grad_points,
                        x_weight, grad_images, (V3 *)dy);
+    return check_launch();
+  }
+  return MR_OK;
+}
+
+void nearest_triangle_plan(int B, int N, int T, int *splits, int *queries_per_lane, int *triangle_tile,
+                           int *workgroup) {
+  const Plan p = tri_plan_of(B, N, T);
+  *splits = p.splits;
+  *queries_per_lane = p.queries_per_lane;
+  *triangle_tile = kTriTile;
+  *workgroup = kThreads;
+}
+
+// records | keys (splits > 1) | the finish pass's partial sums
+size_t nearest_triangle_ws(int B, int N, int T) {
+  const Plan p = tri_plan_of(B, N, T);
+  return tri_records_bytes(B, T) + keys_bytes(p, B, N) + align_up((size_t)B * merge_blocks_of(N) * sizeof(float), 256);
+}
+
+int launch_nearest_triangle_forward(const float *points, const float *vertices, const int32_t *triangles,
+                                    const int32_t *lengths, int B, int N, int V, int T, float *sqdist, int32_t *face,
+                                    float *bary, float *total, void *ws, hipStream_t s) {
+  const Plan p = tri_plan_of(B, N, T);
+  float4 *records = (float4 *)ws;
+  unsigned long long *keys = p.splits > 1 ? (unsigned long long *)((char *)ws + tri_records_bytes(B, T)) : nullptr;
+  float *partials = total ? (float *)((char *)ws + tri_records_bytes(B, T) + keys_bytes(p, B, N)) : nullptr;
+  hipLaunchKernelGGL(k_nt_setup, dim3((unsigned)((T + kThreads - 1) / kThreads), (unsigned)B), dim3(kThreads), 0, s,
+                     (const V3 *)vertices, triangles, V, T, records);
+  int rc = check_launch();
+  if (rc != MR_OK) return rc;
+  const dim3 grid((unsigned)p.query_blocks, (unsigned)p.splits, (unsigned)B);
+  if (p.queries_per_lane == kTriWideQueries)
+    hipLaunchKernelGGL(k_nt_search<F2>, grid, dim3(kThreads), 0, s, points, (const float4 *)records, lengths, N, T,
+                       p.chunk, face, keys);
+  else
+    hipLaunchKernelGGL(k_nt_search<float>, grid, dim3(kThreads), 0, s, points, (const float4 *)records, lengths, N, T,
+                       p.chunk, face, keys);
+  rc = check_launch();
+  if (rc != MR_OK) return rc;
+  const dim3 rows(merge_blocks_of(N), (unsigned)B);
+  if (keys) {   // the lowest key of a query's splits -> its face, -1 without one
+    hipLaunchKernelGGL(k_nearest_merge, rows, dim3(kThreads), 0, s, (const unsigned long long *)keys, p.splits, lengths,
+                       (const int32_t *)nullptr, N, T, (float *)nullptr, face, (float *)nullptr);
+    rc = check_launch();
+    if (rc != MR_OK) return rc;
+  }
+  hipLaunchKernelGGL(k_nt_finish, rows, dim3(kThreads), 0, s, (const V3 *)points, (const float4 *)records, lengths, N, T,
+                     sqdist, face, (V3 *)bary, partials);
+  rc = check_launch();
+  if (rc != MR_OK) return rc;
+  if (total) {
+    hipLaunchKernelGGL(k_nearest_mean, dim3((unsigned)B), dim3(kThreads), 0, s, (const float *)partials,
+                       (int)merge_blocks_of(N), lengths, (const int32_t *)nullptr, N, T, 1.0f, 0, total);
+    rc = check_launch();
+  }
+  return rc;
+}
+
+int launch_nearest_triangle_backward(const float *points, const float *vertices, const int32_t *triangles,
+                                     const int32_t *lengths, int B, int N, int V, int T, const int32_t *face,
+                                     const float *bary, const int32_t *order, const int32_t *offsets,
+                                     const float *grad_points, const float *grad_images, float *dpoints,
+                                     float *dvertices, hipStream_t s) {
+  if (dpoints) {
+    hipLaunchKernelGGL(k_nt_backward_points, dim3(merge_blocks_of(N), (unsigned)B), dim3(kThreads), 0, s,
+                       (const V3 *)points, (const V3 *)vertices, triangles, lengths, N, V, T, face, (const V3 *)bary,
+                       grad_points, grad_images, (V3 *)dpoints);
+    const int rc = check_launch();
+    if (rc != MR_OK) return rc;
+  }
+  if (dvertices) {
+    const dim3 grid((unsigned)((V + kPointsPerBlock - 1) / kPointsPerBlock), (unsigned)B);
+    hipLaunchKernelGGL(k_nt_backward_vertices, grid, dim3(kThreads), 0, s, (const V3 *)points, (const V3 *)vertices,
+                       triangles, lengths, N, V, T, face, (const V3 *)bary, order, offsets, grad_points, grad_images,
+                       (V3 *)dvertices);
     return check_launch();
   }
   return MR_OK;

@@ -1,4 +1,4 @@
-"""Point-cloud losses: nearest neighbours, Chamfer distance and area-weighted surface sampling.
+"""Point-cloud losses: nearest neighbours, Chamfer distance, point-to-mesh distance and area-weighted surface sampling.
 
 The data term for fitting a mesh to 3D data -- a scan, a depth camera's point cloud, another mesh -- next to the
 regularisers of mesh_renderer.regularizers ("Point-cloud losses").  On a HIP device the float32
@@ -6,7 +6,9 @@ clouds go through csrc/nearest.hip: a brute-force nearest-neighbour search that 
 tensor, a fixed-order mean, and a backward without atomics (a gather over an inverted index of the saved
 neighbours), bitwise reproducible in either deterministic mode.  Host tensors and tensors that are not float32 --
 data preparation, the CPU test-suite -- take the equivalent torch expression, chunked over the queries.
-Distances are always computed as (x - y).(x - y), never as |x|^2 + |y|^2 - 2 x.y.
+Distances are always computed as (x - y).(x - y), never as |x|^2 + |y|^2 - 2 x.y.  nearest_triangles and
+point_mesh_distance measure to the mesh's surface itself -- the nearest closed triangle -- with kernels of the same
+file and the same split between the HIP and the torch path.
 """
 import torch
 from torch.autograd.function import once_differentiable
@@ -276,3 +278,186 @@ def sample_surface_points(vertices, triangles, count, generator=None, return_fac
     if single:
         uniforms = uniforms[0]
     return sample_surface_points_from_uniforms(vertices, triangles, uniforms, return_faces=return_faces)
+
+
+# ---- point to mesh: the nearest triangle ----------------------------------------------------------------------------
+
+def _point_mesh_arguments(points, vertices, triangles, lengths):
+    """-> (points [B,N,3], vertices [B,V,3], triangles [T,3] int64 on their device, lengths, whether the batch axis
+    was missing)."""
+    _cloud("points", points)
+    v, tris, single = _mesh(vertices, triangles)
+    if points.dim() != vertices.dim():
+        raise ValueError("points and vertices must both have a batch axis or both lack it, got %s and %s"
+                         % (list(points.shape), list(vertices.shape)))
+    p = points.unsqueeze(0) if single else points
+    if p.shape[0] != v.shape[0]:
+        raise ValueError("points and vertices must have the same batch size, got %s and %s"
+                         % (list(points.shape), list(vertices.shape)))
+    if p.device != v.device:
+        raise RuntimeError("points and vertices must be on the same device")
+    if p.dtype != v.dtype:
+        raise RuntimeError("points and vertices must have the same dtype, got %s and %s" % (p.dtype, v.dtype))
+    if single and torch.is_tensor(lengths) and lengths.dim() == 0:
+        lengths = lengths.reshape(1)
+    return p, v, tris, _lengths("lengths", lengths, p.shape[0], p.shape[1], p), single
+
+
+class _TriangleRecords:
+    """What the search needs of every (image, triangle): a, e0 = b - a, e1 = c - a, e2 = c - b, the dot products and
+    the reciprocals (0 where the denominator is not positive), each [B,T,...]; usable [T]."""
+
+    def __init__(self, v, tris):
+        V = v.shape[1]
+        self.usable = ((tris >= 0) & (tris < V)).all(dim=1)
+        safe = tris.clamp(0, V - 1)
+        a, b, c = (v.index_select(1, safe[:, k]) for k in range(3))
+        self.a, self.e0, self.e1, self.e2 = a, b - a, c - a, c - b
+        self.d00, self.d01, self.d11 = (self.e0 * self.e0).sum(-1), (self.e0 * self.e1).sum(-1), (self.e1 * self.e1).sum(-1)
+        d22 = (self.e2 * self.e2).sum(-1)
+        det = self.d00 * self.d11 - self.d01 * self.d01
+        inverse = lambda x: torch.where(x > 0, 1.0 / x, torch.zeros_like(x))
+        self.idet, self.i00, self.i11, self.i22 = inverse(det), inverse(self.d00), inverse(self.d11), inverse(d22)
+
+    def select(self, pick):
+        """The records as seen by the queries: pick(t [B,T,...]) -> a tensor that broadcasts against [B,rows,...]."""
+        out = object.__new__(_TriangleRecords)
+        for name in ("a", "e0", "e1", "e2", "d00", "d01", "d11", "idet", "i00", "i11", "i22"):
+            setattr(out, name, pick(getattr(self, name)))
+        return out
+
+
+def _triangle_candidates(p, r):
+    """The four candidates of the definition for queries p [...,3] against records r that broadcast with them ->
+    (squared distances [...,4] with +inf for a projection that is no candidate and for NaN, beta [...,4],
+    gamma [...,4]) in the order projection, ab, bc, ca; every distance is |d - (beta e0 + gamma e1)|^2 with d = p - a
+    (the segment bc from d - e0)."""
+    d = p - r.a
+    p0, p1 = (d * r.e0).sum(-1), (d * r.e1).sum(-1)
+    sq = lambda x: (x * x).sum(-1)
+    tab = (p0 * r.i00).clamp(0, 1)
+    tca = (p1 * r.i11).clamp(0, 1)
+    db = d - r.e0
+    tbc = ((db * r.e2).sum(-1) * r.i22).clamp(0, 1)
+    v = (p0 * r.d11 - p1 * r.d01) * r.idet
+    w = (p1 * r.d00 - p0 * r.d01) * r.idet
+    inside = (r.idet > 0) & (v >= 0) & (w >= 0) & (v + w <= 1)
+    inf = torch.full_like(p0, float("inf"))
+    dist = torch.stack([torch.where(inside, sq(d - v[..., None] * r.e0 - w[..., None] * r.e1), inf),
+                        sq(d - tab[..., None] * r.e0), sq(db - tbc[..., None] * r.e2), sq(d - tca[..., None] * r.e1)], -1)
+    dist = torch.where(dist == dist, dist, inf[..., None])   # a NaN never wins
+    zero = torch.zeros_like(tab)
+    return dist, torch.stack([v, tab, 1.0 - tbc, zero], -1), torch.stack([w, zero, tbc, tca], -1)
+
+
+def _nearest_triangles_torch(points, v, tris, lengths):
+    """nearest_triangles as a torch expression on the device and in the dtype of points [B,N,3] / v [B,V,3]: the face
+    is searched chunk by chunk of queries without a graph; the distance to the closest point, its barycentrics held
+    constant (the envelope theorem), is then an ordinary differentiable expression."""
+    B, N, _ = points.shape
+    T = tris.shape[0]
+    dev = points.device
+    n_valid = lengths.long() if lengths is not None else torch.full((B,), N, dtype=torch.int64, device=dev)
+    with torch.no_grad():
+        records = _TriangleRecords(v.detach(), tris)
+        against_all = records.select(lambda t: t[:, None])                       # [B,1,T,...]
+        rows = max(1, _CHUNK_BYTES // max(1, B * T * 12 * points.element_size()))
+        faces, found = [], []
+        for start in range(0, N, rows):
+            dist, _, _ = _triangle_candidates(points.detach()[:, start:start + rows, None, :], against_all)
+            best = dist.min(dim=-1).values.masked_fill(~records.usable[None, None, :], float("inf"))   # [B,rows,T]
+            nearest = best.min(dim=2)                                             # the first of equal minima
+            faces.append(nearest.indices)
+            found.append(nearest.values < float("inf"))
+        face = torch.cat(faces, dim=1)
+        valid = torch.cat(found, dim=1) & (torch.arange(N, device=dev)[None, :] < n_valid[:, None])
+        face = torch.where(valid, face, torch.zeros_like(face))
+        chosen = records.select(lambda t: torch.gather(
+            t, 1, face.reshape(B, N, *[1] * (t.dim() - 2)).expand(B, N, *t.shape[2:])))   # [B,N,...]
+        dist, beta, gamma = _triangle_candidates(points.detach(), chosen)
+        which = dist.min(dim=-1).indices[..., None]
+        beta, gamma = torch.gather(beta, -1, which)[..., 0], torch.gather(gamma, -1, which)[..., 0]
+        bary = torch.stack([(1.0 - (beta + gamma)).clamp(min=0), beta, gamma], -1)
+        bary = torch.where(valid[..., None], bary, torch.zeros_like(bary))
+    # differentiable: |d - (beta e0 + gamma e1)|^2 from the vertices of the chosen face
+    corner = tris.clamp(0, v.shape[1] - 1)[face]                                 # [B,N,3]
+    a, b, c = (torch.gather(v, 1, corner[..., k, None].expand(-1, -1, 3)) for k in range(3))
+    residual = (points - a) - (bary[..., 1:2] * (b - a) + bary[..., 2:3] * (c - a))
+    residual = torch.where(valid[..., None], residual, torch.zeros_like(residual))   # no result: value 0, gradient 0
+    face = torch.where(valid, face, torch.full_like(face, -1))
+    return (residual * residual).sum(-1), face.to(torch.int32), bary
+
+
+class _NearestTriangles(torch.autograd.Function):
+    """Both public functions on the HIP path.  reduce False: (sqdist [B,N], face [B,N], bary [B,N,3]); reduce True:
+    the mean of sqdist over each image's valid queries [B]."""
+
+    @staticmethod
+    def forward(ctx, points, vertices, triangles, lengths, reduce):
+        pd, vd = points.detach().contiguous(), vertices.detach().contiguous()
+        sqdist, face, bary, total = _native.nearest_triangle_forward(pd, vd, triangles, lengths, want_sqdist=not reduce,
+                                                                     want_total=reduce)
+        ctx.reduce = reduce
+        ctx.save_for_backward(pd, vd, triangles, lengths, face, bary)
+        if reduce:
+            return total
+        ctx.mark_non_differentiable(face, bary)
+        return sqdist, face, bary
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad, _face=None, _bary=None):
+        points, vertices, triangles, lengths, face, bary = ctx.saved_tensors
+        want_dp, want_dv = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        none = (None,) * 3
+        if not (want_dp or want_dv):
+            return (None, None) + none
+        index = None
+        if want_dv:   # the (query, corner) entries keyed by the vertex they name, -1 for rows without a face
+            named = triangles[face.clamp(min=0).long()]                          # [B,N,3]
+            named = torch.where(face[..., None] < 0, torch.full_like(named, -1), named)
+            index = _native.nearest_inverted_index(named.reshape(face.shape[0], -1), vertices.shape[1])
+        grad = grad.contiguous()
+        dp, dv = _native.nearest_triangle_backward(
+            points, vertices, triangles, lengths, face, bary, index, grad_points=None if ctx.reduce else grad,
+            grad_images=grad if ctx.reduce else None, want_dpoints=want_dp, want_dvertices=want_dv)
+        return (dp, dv) + none
+
+
+def _device_triangles(tris, V):
+    """int32 for the kernels; an index that int32 cannot hold is outside [0, V) either way."""
+    return torch.where((tris >= 0) & (tris < V), tris, torch.full_like(tris, -1)).to(torch.int32).contiguous()
+
+
+def nearest_triangles(points, vertices, triangles, lengths=None):
+    """points [B,N,3], vertices [B,V,3] (or [N,3], [V,3]: one image, results without the batch axis), triangles [T,3]
+    of any integer dtype (one topology for the batch) -> (sqdist [B,N], face [B,N] int32, bary [B,N,3]): for every
+    point the squared Euclidean distance to the nearest CLOSED triangle (interior, edges and corners), the lowest
+    face that attains it and the barycentrics of the closest point on that face (>= 0, adding up to 1).  A zero-area
+    triangle counts as its edges or its point; a triangle with an index outside [0, V) is never chosen.
+
+    sqdist is differentiable in points and vertices with the barycentrics held constant (the envelope theorem);
+    face and bary are not differentiable.  lengths: an optional integer [B] tensor on the points' device for padded
+    clouds, clamped to [0, N] on the device.  A padded row, and a point for which no triangle compared below +inf
+    (no usable triangle, NaN coordinates), get sqdist 0, face -1, bary 0 and no gradient; padded coordinates
+    influence nothing.  Every other face is a usable triangle's index."""
+    p, v, tris, lengths, single = _point_mesh_arguments(points, vertices, triangles, lengths)
+    if _on_hip_path(p):
+        out = _NearestTriangles.apply(p, v, _device_triangles(tris, v.shape[1]), lengths, False)
+    else:
+        out = _nearest_triangles_torch(p, v, tris, lengths)
+    return tuple(t[0] for t in out) if single else tuple(out)
+
+
+def point_mesh_distance(points, vertices, triangles, lengths=None):
+    """The mean over each image's valid points of nearest_triangles' sqdist -> [B] (a 0-dim tensor without the batch
+    axis); 0 for an image without a valid point or a usable triangle.  The data term for fitting a mesh to a scan
+    without the sampling noise of chamfer_distance against sampled points: the distance is to the surface itself.
+    A fixed-order sum on a HIP device; differentiable in points and vertices, and a gradient that is not required is
+    not computed."""
+    p, v, tris, lengths, single = _point_mesh_arguments(points, vertices, triangles, lengths)
+    if _on_hip_path(p):
+        total = _NearestTriangles.apply(p, v, _device_triangles(tris, v.shape[1]), lengths, True)
+    else:
+        total = _mean_torch(_nearest_triangles_torch(p, v, tris, lengths)[0], lengths, None)
+    return total[0] if single else total
