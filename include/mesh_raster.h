@@ -252,6 +252,30 @@ int mr_render_forward_l1(const float *vertices, const float *transforms, const f
                          const float *target, const uint8_t *target_empty, float *loss, uint8_t *signs,
                          float *partials);
 
+/* mr_render_forward_l1 for a caller that keeps the G-buffer to itself and differentiates the loss to the world-space
+ * vertices only (an explicit opt-in: nothing else calls it).  The image, the loss, the sign codes, the partial sums,
+ * the empty-region map and the records of `backward_private` have the bits mr_render_forward_l1 gives them.  What
+ * differs is the G-buffer, which is PRIVATE to this pair of calls:
+ *   - there is no barycentric plane (no `bary` argument; 12 B/px of stores and, in the backward, of loads less);
+ *   - ids holds -1, not 0, where nothing was drawn;
+ *   - z is scratch (state between the bin rounds of a crowded region), undefined afterwards.
+ * Only mr_shade_backward_l1 with MR_GBUFFER_NORMALISED | MR_GBUFFER_PRIVATE reads such a G-buffer: its lane kernel
+ * rebuilds a covered pixel's barycentrics from the pixel centre and the triangle's edge functions, with the
+ * rasterizer's own un-fused expression and division (the same bits), and tells background by the id.
+ *   backward_private  out, mr_render_forward_l1_private_bytes(B, T, W, H) bytes, 256-byte aligned: the block
+ *                     mr_render_forward calls backward_prepared, followed by the triangles' edge coefficients and the
+ *                     pixel-centre tables.  Handed to mr_shade_backward_l1 as `prepared`; serves ONE backward call. */
+size_t mr_render_forward_l1_private_bytes(int B, int T, int W, int H);
+int mr_render_forward_l1_private(const float *vertices, const float *transforms, const float *normals,
+                                 const float *diffuse, const int32_t *triangles,
+                                 const float *light_positions, const float *light_intensities,
+                                 const float *ambient, int B, int V, int T, int W, int H, int L,
+                                 float *clip, int32_t *ids, float *z, float *rgba, uint8_t *rgba_u8,
+                                 void *corner_records, void *backward_private, uint8_t *empty_regions,
+                                 void *workspace, size_t workspace_bytes, void *stream,
+                                 const float *target, const uint8_t *target_empty, float *loss, uint8_t *signs,
+                                 float *partials);
+
 /* Backward of mr_shade_forward AND of the rasterizer underneath it, in one pass
  * over the G-buffer (reads 32 B/px).  All outputs are zeroed here.
  *   drgba        [B,H,W,4] f32  dL/d(rgba); the alpha channel's gradient is ignored
@@ -319,6 +343,11 @@ int mr_shade_backward(const float *drgba, const int32_t *ids, const float *bary,
  * and the d / d alpha terms: the same bits with ~20 % fewer vector instructions per pixel.  0 = any
  * G-buffer (e.g. one the caller edited). */
 #define MR_GBUFFER_NORMALISED 1
+/* bit 1 = MR_GBUFFER_PRIVATE (mr_shade_backward_l1 only, together with MR_GBUFFER_NORMALISED): ids is the private id
+ * plane of mr_render_forward_l1_private (-1 = nothing drawn), `bary` is not read (NULL will do) and `prepared` is
+ * that call's backward_private block.  Vertex gradients only (dnormals, ddiffuse, dclip, light_grads NULL;
+ * transforms, corner_records and the adjacency given), one to four lights, not deterministic: MR_EINVAL otherwise. */
+#define MR_GBUFFER_PRIVATE 2
 
 /* mr_shade_backward for an upstream gradient that is the backward of mr_l1_loss_forward(rgba,
  * target): instead of the [B,H,W,4] float image mr_l1_loss_backward would write (16 B/px) it takes

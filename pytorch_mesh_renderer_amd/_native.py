@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("MR_NATIVE_LIB_PATH") or os.path.join(_CSRC, "libmesh_
 
 ABI_VERSION = 356
 GBUFFER_NORMALISED = 1   # mesh_raster.h, MR_GBUFFER_NORMALISED
+GBUFFER_PRIVATE = 2      # MR_GBUFFER_PRIVATE
 TIMER_RASTER_FORWARD, TIMER_SHADE_BACKWARD, TIMER_SHADE_FORWARD, TIMER_RASTER_BACKWARD, TIMER_L1_FORWARD = 0, 1, 2, 3, 4
 MR_OK, MR_EINVAL, MR_EWORKSPACE, MR_ELAUNCH = 0, -1, -2, -3
 _ERR = {MR_EINVAL: "invalid argument", MR_EWORKSPACE: "workspace too small or misaligned",
@@ -309,6 +310,15 @@ def lib():
             L.mr_time_no_kernel.restype = ci
         except AttributeError as e:   # the loss-in-forward entry points came without an ABI version bump
             raise NativeLibraryError("%s lacks mr_render_forward_l1 (%s): rebuild it (make -C "
+                                     "pytorch_mesh_renderer_amd/csrc)" % (LIB_PATH, e))
+        try:
+            L.mr_render_forward_l1_private_bytes.argtypes = [ci] * 4
+            L.mr_render_forward_l1_private_bytes.restype = sz
+            # mr_render_forward_l1 without `bary` and `want_z`
+            L.mr_render_forward_l1_private.argtypes = [vp] * 8 + [ci] * 6 + [vp] * 9 + [sz, vp] + [vp] * 5
+            L.mr_render_forward_l1_private.restype = ci
+        except AttributeError as e:   # the private G-buffer entry points came without an ABI version bump
+            raise NativeLibraryError("%s lacks mr_render_forward_l1_private (%s): rebuild it (make -C "
                                      "pytorch_mesh_renderer_amd/csrc)" % (LIB_PATH, e))
         try:
             L.mr_mesh_regularizer_workspace_bytes.argtypes = [ci] * 3
@@ -625,7 +635,7 @@ def vertex_transform(vertices, transforms):
 
 def render_forward(vertices, transforms, normals, diffuse, triangles, light_positions, light_intensities,
                    ambient, width, height, want_z=True, want_u8=False, prepare_backward=False, want_empty_regions=False,
-                   l1_target=None, l1_target_empty=None):
+                   l1_target=None, l1_target_empty=None, private_gbuffer=False):
     """render()'s forward from world-space vertices: clip-space transform, rasterizer and shading
     (the shading is the epilogue of the rasterizer's tile walk: one pass over the pixels)
     -> (clip, ids, bary, z, rgba, corner_records); with want_z=False the depth plane is not written
@@ -643,7 +653,14 @@ def render_forward(vertices, transforms, normals, diffuse, triangles, light_posi
     l1_target ([B,H,W,4] float32, contiguous; mr_render_forward_l1): the same pass also compares every pixel it shades
     with the target -- the very LAST value is then (loss, signs), what l1_loss_forward(rgba, l1_target) returns (the
     sum is grouped by region instead of by row: equal to rounding), and no loss kernel has to read the image back.
-    l1_target_empty: the target's image_empty_regions map or None; regions empty on both sides are not read."""
+    l1_target_empty: the target's image_empty_regions map or None; regions empty on both sides are not read.
+
+    private_gbuffer=True (mr_render_forward_l1_private; needs l1_target and prepare_backward, want_z=False): the caller
+    keeps the G-buffer to itself and will hand it to shade_backward(..., l1_signs=, prepared=, private_gbuffer=True) only.
+    No barycentric plane is written -- `bary` comes back as None -- and `ids` says -1, not 0, where nothing was drawn;
+    image, loss, sign codes and the empty-region map have the bits they have without it."""
+    if private_gbuffer and (l1_target is None or not prepare_backward or want_z):
+        raise ValueError("private_gbuffer needs l1_target and prepare_backward, and leaves no depth plane")
     tensors = [vertices, transforms, normals, diffuse, triangles, light_positions, light_intensities]
     _chk("vertices", vertices, _F32, None, None, 3)
     _chk("triangles", triangles, _I32, None, 3)
@@ -667,13 +684,16 @@ def render_forward(vertices, transforms, normals, diffuse, triangles, light_posi
     nl = light_positions.shape[1]
     clip = torch.empty(B, V, 4, dtype=torch.float32, device=dev)
     ids = torch.empty(B, height, width, dtype=torch.int32, device=dev)
-    bary = torch.empty(B, height, width, 3, dtype=torch.float32, device=dev)
+    bary = None if private_gbuffer else torch.empty(B, height, width, 3, dtype=torch.float32, device=dev)
     z = torch.empty(B, height, width, dtype=torch.float32, device=dev)
     rgba = torch.empty(B, height, width, 4, dtype=torch.float32, device=dev)
     frames = torch.empty(B, height, width, 4, dtype=torch.uint8, device=dev) if want_u8 else None
     with torch.cuda.device(dev):
         records = _aligned_bytes(L.mr_shade_forward_workspace_bytes(B, V, T, width, height), dev)
-        prepared = _aligned_bytes(L.mr_shade_backward_prepared_bytes(B, T), dev) if prepare_backward else None
+        if private_gbuffer:
+            prepared = _aligned_bytes(L.mr_render_forward_l1_private_bytes(B, T, width, height), dev)
+        else:
+            prepared = _aligned_bytes(L.mr_shade_backward_prepared_bytes(B, T), dev) if prepare_backward else None
         empty = (torch.empty(B, (height + 63) // 64, (width + 63) // 64, dtype=torch.uint8, device=dev)
                  if want_empty_regions else None)
         need = L.mr_rasterize_forward_workspace_bytes(B, V, T, width, height)
@@ -691,7 +711,11 @@ def render_forward(vertices, transforms, normals, diffuse, triangles, light_posi
             loss = torch.empty((), dtype=torch.float32, device=dev)
             signs = torch.empty(B * height * width, dtype=torch.uint8, device=dev)
             partials = torch.empty(max(1, L.mr_render_forward_l1_partials(B, width, height)), dtype=torch.float32, device=dev)
-            rc = L.mr_render_forward_l1(*args, _ptr(l1_target), _ptr(l1_target_empty), _ptr(loss), _ptr(signs), _ptr(partials))
+            l1_args = (_ptr(l1_target), _ptr(l1_target_empty), _ptr(loss), _ptr(signs), _ptr(partials))
+            if private_gbuffer:   # (no `bary`, no `want_z`)
+                rc = L.mr_render_forward_l1_private(*(args[:16] + (args[17],) + args[19:] + l1_args))
+            else:
+                rc = L.mr_render_forward_l1(*args, *l1_args)
             l1 = (loss, signs)
     _check(rc, "mr_render_forward")
     out = (clip, ids, bary, (z if want_z else None), rgba, records) + ((frames,) if want_u8 else ())
@@ -1544,7 +1568,8 @@ def attribute_derivatives(ids, bary, clip, triangles, attributes, attribute_tria
 def shade_backward(drgba, ids, bary, clip, normals, positions, diffuse, triangles, light_positions,
                    light_intensities, ambient, corner_records=None, adjacency=None, l1_signs=None,
                    transforms=None, want_light_grads=True, want_normal_grads=True, want_diffuse_grads=True,
-                   normalised_gbuffer=False, want_clip_grads=True, prepared=None, empty_regions=None):
+                   normalised_gbuffer=False, want_clip_grads=True, prepared=None, empty_regions=None,
+                   private_gbuffer=False):
     """_shade_backward_call for any light count up to shade_max_lights().  The kernels keep the light
     gradients' 6 L sums in registers, four lights per call; with more lights the vertex-side gradients
     come from one call over all lights (a run-time loop, no light gradients) and each group of four
@@ -1556,7 +1581,7 @@ def shade_backward(drgba, ids, bary, clip, normals, positions, diffuse, triangle
     kw = dict(corner_records=corner_records, adjacency=adjacency, l1_signs=l1_signs, transforms=transforms,
               want_normal_grads=want_normal_grads, want_diffuse_grads=want_diffuse_grads,
               normalised_gbuffer=normalised_gbuffer, want_clip_grads=want_clip_grads, prepared=prepared,
-              empty_regions=empty_regions)
+              empty_regions=empty_regions, private_gbuffer=private_gbuffer)
     fast = shade_fast_lights() if nl > 4 else nl
     if nl <= fast or not want_light_grads:
         return _shade_backward_call(drgba, ids, bary, clip, normals, positions, diffuse, triangles,
@@ -1581,7 +1606,8 @@ def shade_backward(drgba, ids, bary, clip, normals, positions, diffuse, triangle
 def _shade_backward_call(drgba, ids, bary, clip, normals, positions, diffuse, triangles, light_positions,
                          light_intensities, ambient, corner_records=None, adjacency=None, l1_signs=None,
                          transforms=None, want_light_grads=True, want_normal_grads=True, want_diffuse_grads=True,
-                         normalised_gbuffer=False, want_clip_grads=True, prepared=None, empty_regions=None):
+                         normalised_gbuffer=False, want_clip_grads=True, prepared=None, empty_regions=None,
+                         private_gbuffer=False):
     """-> (dclip [B,V,4], dnormals, dpositions, ddiffuse [B,V,3], dlight_positions,
     dlight_intensities [B,L,3], dambient [B,3] or None); with want_light_grads=False the last three
     are None and the kernel leaves their accumulation out; want_normal_grads / want_diffuse_grads=False
@@ -1602,7 +1628,17 @@ def _shade_backward_call(drgba, ids, bary, clip, normals, positions, diffuse, tr
     pass where the library has that variant (9 sums per triangle instead of 18).
 
     prepared: the block render_forward(..., prepare_backward=True) returned for these inputs (or None).
-    empty_regions: render_forward(..., want_empty_regions=True)'s map for this G-buffer (or None)."""
+    empty_regions: render_forward(..., want_empty_regions=True)'s map for this G-buffer (or None).
+
+    private_gbuffer: ids and prepared are what render_forward(..., private_gbuffer=True) returned (MR_GBUFFER_PRIVATE);
+    bary is None.  Sign-coded upstream, vertex gradients only, one to four lights: anything else is refused."""
+    if private_gbuffer:
+        if bary is not None or prepared is None or l1_signs is None or not normalised_gbuffer:
+            raise ValueError("a private G-buffer has no barycentrics and comes with its prepared block and sign codes")
+        _chk("triangle ids", ids, _I32, clip.shape[0], None, None)
+        if prepared.numel() < lib().mr_render_forward_l1_private_bytes(clip.shape[0], triangles.shape[0], ids.shape[2], ids.shape[1]):
+            raise ValueError("prepared must be the block render_forward(private_gbuffer=True) returned for these inputs")
+        bary = ids   # (stands in below where every tensor is checked; not passed on)
     if empty_regions is not None:
         _chk("empty_regions", empty_regions, _U8, clip.shape[0], (ids.shape[1] + 63) // 64, (ids.shape[2] + 63) // 64)
         empty_regions = empty_regions.contiguous()
@@ -1616,7 +1652,7 @@ def _shade_backward_call(drgba, ids, bary, clip, normals, positions, diffuse, tr
     B, V, _ = _chk_mesh(clip, triangles)
     for name, t in (("normals", normals), ("positions", positions), ("diffuse colors", diffuse)):
         _chk(name, t, _F32, B, V, 3)
-    h, w = _chk_gbuffer(ids, bary, B)
+    h, w = (ids.shape[1], ids.shape[2]) if private_gbuffer else _chk_gbuffer(ids, bary, B)
     _chk_lights(light_positions, light_intensities, ambient, B, shade_max_lights())
     if l1_signs is None:
         _chk("upstream gradient", drgba, _F32, B, h, w, 4)
@@ -1636,6 +1672,8 @@ def _shade_backward_call(drgba, ids, bary, clip, normals, positions, diffuse, tr
     (drgba, ids, bary, clip, normals, positions, diffuse, triangles, light_positions,
      light_intensities) = [t.contiguous() for t in tensors[:10]]
     ambient = ambient.contiguous() if ambient is not None else None
+    if private_gbuffer:
+        bary = None
     B, H, W = ids.shape
     V, T, nl = normals.shape[1], triangles.shape[0], light_positions.shape[1]
     # one allocation, laid out back to back: the library then zeroes all outputs with one memset
@@ -1657,7 +1695,8 @@ def _shade_backward_call(drgba, ids, bary, clip, normals, positions, diffuse, tr
     tail = (B, V, T, W, H, nl, _ptr(dclip), _ptr(dn), _ptr(dp), _ptr(dd), _ptr(lg), _ptr(corner_records),
             _ptr(adjacency[0]) if adjacency is not None else None,
             _ptr(adjacency[1]) if adjacency is not None else None, _ptr(transforms),
-            GBUFFER_NORMALISED if normalised_gbuffer else 0, _ptr(prepared), _ptr(empty_regions))
+            (GBUFFER_NORMALISED if normalised_gbuffer else 0) | (GBUFFER_PRIVATE if private_gbuffer else 0),
+            _ptr(prepared), _ptr(empty_regions))
     with torch.cuda.device(dev):
         _arm_timer(TIMER_SHADE_BACKWARD)
         _sync_deterministic()

@@ -317,6 +317,36 @@ int mr_render_forward_l1(const float *vertices, const float *transforms, const f
                                       target, target_empty, loss, signs, partials, (hipStream_t)stream);
 }
 
+size_t mr_render_forward_l1_private_bytes(int B, int T, int W, int H) {
+  if (B < 0 || T < 0 || W < 1 || H < 1 || W > 65535 || H > 65535) return 0;
+  return mr::shade_backward_private_bytes(B, T, W, H);
+}
+
+int mr_render_forward_l1_private(const float *vertices, const float *transforms, const float *normals,
+                                 const float *diffuse, const int32_t *triangles, const float *light_positions,
+                                 const float *light_intensities, const float *ambient, int B, int V, int T, int W,
+                                 int H, int L, float *clip, int32_t *ids, float *z, float *rgba, uint8_t *rgba_u8,
+                                 void *corner_records, void *backward_private, uint8_t *empty_regions, void *workspace,
+                                 size_t workspace_bytes, void *stream, const float *target, const uint8_t *target_empty,
+                                 float *loss, uint8_t *signs, float *partials) {
+  if (bad_dims(B, V, T, W, H) || T < 1 || V < 1 || L < 1 || L > mr::shade_max_lights())
+    return MR_EINVAL;
+  if (!loss) return MR_EINVAL;
+  if (B == 0) return mr::zero_async(loss, sizeof(float), (hipStream_t)stream) == hipSuccess ? MR_OK : mr::check_launch();
+  if (!vertices || !transforms || !normals || !diffuse || !triangles || !light_positions ||
+      !light_intensities || !clip || !ids || !z || !rgba || !corner_records || !backward_private ||
+      ((uintptr_t)corner_records & 127u) || ((uintptr_t)clip & 15u) || ((uintptr_t)transforms & 15u) ||
+      ((uintptr_t)rgba_u8 & 3u) || ((uintptr_t)backward_private & 255u) ||
+      !target || ((uintptr_t)target & 15u) || !signs || !partials)
+    return MR_EINVAL;
+  const int rc = check_ws(workspace, workspace_bytes, mr::raster_forward_ws(B, V, T, W, H));
+  if (rc != MR_OK) return rc;
+  return mr::launch_render_forward_l1(vertices, transforms, normals, diffuse, triangles, light_positions,
+                                      light_intensities, ambient, B, V, T, W, H, L, clip, ids, nullptr, z,
+                                      /*want_z=*/0, rgba, rgba_u8, corner_records, backward_private, empty_regions, workspace,
+                                      target, target_empty, loss, signs, partials, (hipStream_t)stream, true);
+}
+
 size_t mr_shade_forward_workspace_bytes(int B, int V, int T, int W, int H) {
   if (bad_dims(B, V, T, W, H)) return 0;
   return mr::shade_forward_ws(B, V, T, W, H);
@@ -379,10 +409,12 @@ int mr_shade_backward_l1(const uint8_t *signs, const float *upstream, const int3
                          void *prepared, const uint8_t *empty_regions, void *workspace, size_t workspace_bytes,
                          void *stream) {
   if (bad_dims(B, V, T, W, H) || T < 1 || V < 1 || L < 1 || L > mr::shade_max_lights() ||
-      (gbuffer_flags & ~MR_GBUFFER_NORMALISED))
+      (gbuffer_flags & ~(MR_GBUFFER_NORMALISED | MR_GBUFFER_PRIVATE)))
     return MR_EINVAL;
+  const bool private_gbuffer = (gbuffer_flags & MR_GBUFFER_PRIVATE) != 0;   /* no barycentric plane: `bary` is not read */
+  if (private_gbuffer && (!(gbuffer_flags & MR_GBUFFER_NORMALISED) || !prepared)) return MR_EINVAL;
   if (B == 0) return MR_OK;
-  if (!signs || !upstream || !ids || !bary || !clip || !normals || !positions || !diffuse || !triangles ||
+  if (!signs || !upstream || !ids || (!bary && !private_gbuffer) || !clip || !normals || !positions || !diffuse || !triangles ||
       !light_positions || !light_intensities || (!dclip && !transforms) || !dpositions)
     return MR_EINVAL;
   if ((!dnormals || !ddiffuse) && !vertex_offsets) return MR_EINVAL;  /* only the per-vertex gather can leave outputs out */

@@ -160,6 +160,22 @@ inline size_t fold_prepared_bytes(int B, int T) {
   return fold_prepared_recs_bytes(B, T) + align_up((size_t)B * T * kFoldAccStride * sizeof(float), 256);
 }
 
+// The PRIVATE form of that block (mr_render_forward_l1_private: a G-buffer without a barycentric plane, kept by the
+// caller's own backward): behind the records and the accumulator rows it also carries what the lane kernel needs to
+// rebuild a pixel's barycentrics -- EdgeRec[B*T], the sign-corrected adjugate m[9] the rasterizer's edge functions are
+// made of (edge i = m[3 i] x + m[3 i + 1] y + m[3 i + 2]; k_setup holds it in registers), and the rasterizer's own
+// pixel-centre tables, W + H floats (binary64 expressions rounded once: the backward reads the very values).
+struct alignas(16) EdgeRec {
+  float4 q[3];   // m0 m1 m2 m3 | m4 m5 m6 m7 | m8 - - -
+};
+inline size_t fold_private_edges_offset(int B, int T) { return fold_prepared_bytes(B, T); }
+inline size_t fold_private_tables_offset(int B, int T) {
+  return fold_private_edges_offset(B, T) + align_up((size_t)B * T * sizeof(EdgeRec), 256);
+}
+inline size_t fold_private_bytes(int B, int T, int W, int H) {
+  return fold_private_tables_offset(B, T) + align_up(((size_t)W + H) * sizeof(float), 256);
+}
+
 // Fills CornerRec[B*T] from the three [B,V,3] attribute arrays (defined in shade.hip).
 int launch_corner_setup(const float *normals, const float *positions, const float *diffuse,
                         const int32_t *tris, int B, int V, int T, CornerRec *out, hipStream_t s);

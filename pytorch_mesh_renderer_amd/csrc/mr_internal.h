@@ -190,7 +190,9 @@ int launch_render_forward_l1(const float *vertices, const float *transforms, con
                              int L, float *clip, int32_t *ids, float *bary, float *z, int want_z, float *rgba,
                              uint8_t *rgba_u8, void *corner_records, void *backward_prepared, uint8_t *empty_regions, void *ws,
                              const float *target, const uint8_t *target_empty, float *loss, uint8_t *signs, float *partials,
-                             hipStream_t s);
+                             hipStream_t s, bool private_gbuffer = false);
+// the prepared block of mr_render_forward_l1_private (corner_rec.h: fold_private_bytes)
+size_t shade_backward_private_bytes(int B, int T, int W, int H);
 // the G-buffer and the specular term's across-pixels norms (norms2 [B,L], L <= 4) in one pass (raster_forward.hip)
 size_t rasterize_specular_norms_ws(int B, int V, int T, int W, int H);
 int launch_rasterize_specular_norms(const float *clip, const int32_t *tris, const float *normals, const float *positions,

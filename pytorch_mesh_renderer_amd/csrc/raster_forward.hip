@@ -133,6 +133,10 @@ struct SetupAttributes {
   // waiting for a launch of its own to have written them: one launch and one dependent round trip less per step.
   const float4 *__restrict__ xf = nullptr;     // [B][4] rows of the clip-space transforms, or nullptr: `clip` is an input
   float4 *__restrict__ clip_out = nullptr;     // [B,V,4]
+  // The private form of the prepared block (corner_rec.h: fold_private_bytes; with fold_recs): the thread also leaves its
+  // triangle's EdgeRec, and the launch's pixel-centre tables live at pxy_out (W + H floats) instead of in the workspace.
+  EdgeRec *__restrict__ edge_recs = nullptr;
+  float *pxy_out = nullptr;
 };
 
 // Heaviest regions first (round 3).  k_raster's workgroups cost anything between ~5 us (background)
@@ -261,6 +265,11 @@ __global__ __launch_bounds__(kThreads) void k_setup(
           float pull[12];
           load_pull_rows(attrs.fold_transforms, b, pull);
           store_fold_record(corner_values, u, 1.0f / fabsf(det), attrs.fold_recs + gid, pull);
+          if (attrs.edge_recs) {
+            attrs.edge_recs[gid].q[0] = make_float4(m0, m1, m2, m3);
+            attrs.edge_recs[gid].q[1] = make_float4(m4, m5, m6, m7);
+            attrs.edge_recs[gid].q[2] = make_float4(m8, 0.0f, 0.0f, 0.0f);
+          }
         }
       }
     }
@@ -707,6 +716,9 @@ struct RasterShade {
   uint8_t *__restrict__ l1_signs = nullptr;           // [B*H*W]: a pixel's four 2-bit sign codes, as mr_l1_loss_forward lays them out
   float *__restrict__ l1_partials = nullptr;          // [n_regions]: sum |d| of the region's pixels times l1_inv_n (closed by k_l1_finish)
   float l1_inv_n = 0.0f;                              // 1 / (4 B H W)
+  // (with target) the G-buffer stays with the caller's own backward: no barycentric plane (`bary` is not touched), ids
+  // -1 where nothing was drawn -- k_raster's NOBARY
+  bool no_bary = false;
 };
 
 #ifndef MR_RASTER_STORE_AUX
@@ -791,7 +803,12 @@ struct RasterShade {
 // cache.  64 slots = 7 KB more LDS: five workgroups per CU instead of six.  Chosen on the host (launch_k_raster_probe).
 // L1 (SHADE only): the epilogue also compares the pixel with RasterShade::target -- see there.  Everything it adds sits
 // under `if constexpr (L1)`: the other instantiations are the code they were.
-template <int R, int PROBE, bool SHADE, int INTERP = 0, int AX = 0, int XREC = 0, bool NORMS = false, bool L1 = false>
+// NOBARY (L1 only): the G-buffer of a caller that keeps it to itself (RasterShade::no_bary) -- no barycentric plane is
+// written, and the id plane says -1, not 0, where nothing was drawn: the shading backward's lane kernel rebuilds a covered
+// pixel's barycentrics from its centre and its triangle's edge functions (shade.hip: ShadeFoldLaneNoBaryFn<L>) and
+// tells background by the id alone.  Image, loss, sign codes, partial sums and the empty-region map keep their bits.
+template <int R, int PROBE, bool SHADE, int INTERP = 0, int AX = 0, int XREC = 0, bool NORMS = false, bool L1 = false,
+          bool NOBARY = false>
 __global__ __launch_bounds__(kThreads, SHADE ? (XREC ? MR_RASTER_XREC_WAVES : L1 ? MR_RASTER_SHADE_L1_WAVES : MR_RASTER_SHADE_WAVES) : NORMS ? MR_RASTER_NORMS_WAVES : INTERP >= 12 ? 4 : INTERP ? MR_RASTER_INTERP_WAVES : MR_RASTER_WAVES) void k_raster(
     const TriRec *__restrict__ recs, const TriBox *__restrict__ bbs,
     const float *__restrict__ pxtab, const float *__restrict__ pytab, int T, int W, int H,
@@ -806,6 +823,7 @@ __global__ __launch_bounds__(kThreads, SHADE ? (XREC ? MR_RASTER_XREC_WAVES : L1
   static_assert(XREC == 0 || (SHADE && XREC % 4 == 0), "extra record slots: the shading epilogue's");
   static_assert(!SHADE || PROBE == 0, "the shading epilogue has no timing probes");
   static_assert(!L1 || SHADE, "the loss compares the shaded pixel: the shading epilogue's");
+  static_assert(!NOBARY || L1, "the private G-buffer exists on the loss-in-forward route only");
   static_assert(INTERP == 0 || (!SHADE && PROBE == 0 && INTERP % 4 == 0 && INTERP <= 16), "one epilogue at a time");
   static_assert(AX == 0 || (INTERP > 0 && AX <= INTERP && AX > INTERP - 4), "a fixed attribute count belongs to its padded variant");
   static_assert(!NORMS || (INTERP == 8 && AX == 6), "the norm epilogue interpolates normals and positions");
@@ -959,7 +977,8 @@ __global__ __launch_bounds__(kThreads, SHADE ? (XREC ? MR_RASTER_XREC_WAVES : L1
   constexpr int kRsrcWord3 = 0x00020000;  // raw 32-bit buffer on gfx9-family targets
   const __amdgpu_buffer_rsrc_t rs_ids = __builtin_amdgcn_make_buffer_rsrc(ids + region_pix, 0, 0x7fffffff, kRsrcWord3);
   const __amdgpu_buffer_rsrc_t rs_z = __builtin_amdgcn_make_buffer_rsrc(zbuf + region_pix, 0, 0x7fffffff, kRsrcWord3);
-  const __amdgpu_buffer_rsrc_t rs_bary = __builtin_amdgcn_make_buffer_rsrc(bary + 3 * region_pix, 0, 0x7fffffff, kRsrcWord3);
+  const __amdgpu_buffer_rsrc_t rs_bary =
+      __builtin_amdgcn_make_buffer_rsrc(NOBARY ? nullptr : bary + 3 * region_pix, 0, NOBARY ? 0 : 0x7fffffff, kRsrcWord3);
   // RGBA rows are flipped (render.py:384-386: image row H-1-y shows G-buffer row y).  The descriptor
   // is anchored at the image row of the region's LAST G-buffer row -- the lowest address the region
   // writes; for a ragged top region that row lies above the image and only serves as an origin --
@@ -1090,10 +1109,11 @@ __global__ __launch_bounds__(kThreads, SHADE ? (XREC ? MR_RASTER_XREC_WAVES : L1
     }
     for (int y = wave * kRowsPerInst + lane / R; y < R; y += kWaves * kRowsPerInst) {
       const unsigned pix = (unsigned)(y * W + x);
-      __builtin_amdgcn_raw_buffer_store_b32(0u, rs_ids, pix * 4u, 0, MR_RASTER_STORE_AUX_IDS);
+      __builtin_amdgcn_raw_buffer_store_b32(NOBARY ? ~0u : 0u, rs_ids, pix * 4u, 0, MR_RASTER_STORE_AUX_IDS);
       if (!EPI || shade.keep_z)
         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, 1.0f), rs_z, pix * 4u, 0, MR_RASTER_STORE_AUX_Z);
-      __builtin_amdgcn_raw_buffer_store_b96(v3u{0u, 0u, 0u}, rs_bary, pix * 12u, 0, MR_RASTER_STORE_AUX);
+      if constexpr (!NOBARY)
+        __builtin_amdgcn_raw_buffer_store_b96(v3u{0u, 0u, 0u}, rs_bary, pix * 12u, 0, MR_RASTER_STORE_AUX);
       if constexpr (SHADE) {
         typedef unsigned v4u __attribute__((ext_vector_type(4)));
         __builtin_amdgcn_raw_buffer_store_b128(v4u{0u, 0u, 0u, 0u}, rs_rgba, (unsigned)((R - 1 - y) * W + x) * 16u, 0,
@@ -1197,9 +1217,26 @@ __global__ __launch_bounds__(kThreads, SHADE ? (XREC ? MR_RASTER_XREC_WAVES : L1
         st.ent = 0;
         st.z = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_z, lane_pix * 4u, tile_pix * 4, 0));
         st.id = (int)__builtin_amdgcn_raw_buffer_load_b32(rs_ids, lane_pix * 4u, tile_pix * 4, 0);
+        if constexpr (NOBARY) {
+          // no plane to read back: the earlier round's winner (if any: -1 came back as it was stored) is evaluated again,
+          // the depth loop's expression on the triangle's own record -- the same edge values, the same correctly rounded
+          // quotients (div3_common_denominator's two paths agree bit for bit), so the same barycentrics
+          st.b0 = 0.0f; st.b1 = 0.0f; st.b2 = 0.0f;
+          if (st.id >= 0) {
+            const TriRec *rp = img_recs + st.id;
+            const float4 ra = rp->a, rb = rp->b;
+            const float m8 = rp->c.x;
+            const float e0 = (ra.x * px + ra.z * py) + rb.x;
+            const float e1 = (ra.y * px + ra.w * py) + rb.y;
+            const float e2 = (rb.z * px + rb.w * py) + m8;
+            const float s = (e0 + e1) + e2;
+            st.b0 = e0 / s; st.b1 = e1 / s; st.b2 = e2 / s;
+          }
+        } else {
         st.b0 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_bary, lane_pix * 12u, tile_pix * 12, 0));
         st.b1 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_bary, lane_pix * 12u + 4u, tile_pix * 12, 0));
         st.b2 = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs_bary, lane_pix * 12u + 8u, tile_pix * 12, 0));
+        }
       }
       const unsigned all_words = (PROBE & 16) ? 0u  // timing probe: no coverage, no depth
                                               : (unsigned)__ballot(my_word != 0u) & ((1u << kMaskWords) - 1u);
@@ -1542,11 +1579,12 @@ __global__ __launch_bounds__(kThreads, SHADE ? (XREC ? MR_RASTER_XREC_WAVES : L1
         // 768 B of barycentrics) instead of four 64- / 192-byte runs.  The image comes out scrambled.
         const unsigned st_lane = ((PROBE & 64) && R == 64) ? (unsigned)lane : lane_pix;
         const int st_tile = ((PROBE & 64) && R == 64) ? (ty * kTileH + tx) * W : tile_pix;
-        __builtin_amdgcn_raw_buffer_store_b32((unsigned)max(st.id, 0), rs_ids, st_lane * 4u, st_tile * 4,
+        __builtin_amdgcn_raw_buffer_store_b32(NOBARY ? (unsigned)st.id : (unsigned)max(st.id, 0), rs_ids, st_lane * 4u, st_tile * 4,
                                               (PROBE & 64) ? MR_RASTER_STORE_AUX : MR_RASTER_STORE_AUX_IDS);
         if (!EPI || !last_round || shade.keep_z)  // workgroup-uniform
           __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, st.z), rs_z, st_lane * 4u, st_tile * 4, MR_RASTER_STORE_AUX_Z);
-        if constexpr (stage) {
+        if constexpr (NOBARY) {   // the barycentrics stay in registers: the epilogue has used them, nobody reads a plane
+        } else if constexpr (stage) {
           typedef float v4f __attribute__((ext_vector_type(4)));
           typedef unsigned v4u __attribute__((ext_vector_type(4)));
           float *slot = s_ent + (kBin2Cap * kEntryDw - kWaves * kStageDw) + wave * kStageDw + 3 * lane;
@@ -1866,9 +1904,10 @@ struct RasterArgs {
   RasterShade shade;  // rgba == nullptr: G-buffer only
 };
 
-template <int R, int PROBE, bool SHADE = false, int INTERP = 0, int AX = 0, int XREC = 0, bool NORMS = false, bool L1 = false>
+template <int R, int PROBE, bool SHADE = false, int INTERP = 0, int AX = 0, int XREC = 0, bool NORMS = false, bool L1 = false,
+          bool NOBARY = false>
 void launch_k_raster(const RasterArgs &a, dim3 grid, hipStream_t s) {
-  hipLaunchKernelGGL((k_raster<R, PROBE, SHADE, INTERP, AX, XREC, NORMS, L1>), grid, dim3(kThreads), 0, s, a.recs, a.bbs, a.pxtab, a.pytab, a.T,
+  hipLaunchKernelGGL((k_raster<R, PROBE, SHADE, INTERP, AX, XREC, NORMS, L1, NOBARY>), grid, dim3(kThreads), 0, s, a.recs, a.bbs, a.pxtab, a.pytab, a.T,
                      a.W, a.H, a.regions_x, a.per_image, a.n_regions, a.per_xcd, a.cell_ids, a.cell_count,
                      a.cell_split, a.cells_x, a.cells_per_image, a.region_ids, a.region_count, a.order_count,
                      a.order_list, a.ids, a.bary, a.z, a.shade);
@@ -1879,6 +1918,10 @@ void launch_k_raster_probe(const RasterArgs &a, dim3 grid, hipStream_t s) {
   if (a.shade.rgba) {
     // crowded launches (triangles per 64 x 64 pixels of image): the instantiation with extra record slots, see XREC
     const bool crowded = MR_RASTER_XREC > 0 && R == 64 && (double)a.T * 4096.0 >= (double)MR_RASTER_XREC_DENSITY * a.W * a.H;
+    if (a.shade.l1_partials && a.shade.no_bary) {   // ... and a G-buffer private to the caller: no barycentric plane (NOBARY)
+      if (crowded) return launch_k_raster<R, 0, true, 0, 0, (R == 64 ? MR_RASTER_XREC : 0), false, true, true>(a, grid, s);
+      return launch_k_raster<R, 0, true, 0, 0, 0, false, true, true>(a, grid, s);
+    }
     if (a.shade.l1_partials) {   // the loss against a named target inside the epilogue: the same choice of record slots
       if (crowded) return launch_k_raster<R, 0, true, 0, 0, (R == 64 ? MR_RASTER_XREC : 0), false, true>(a, grid, s);
       return launch_k_raster<R, 0, true, 0, 0, 0, false, true>(a, grid, s);
@@ -1929,6 +1972,10 @@ int raster_forward(const float *clip, const int32_t *tris, int B, int V, int T, 
   p += align_up((size_t)W * sizeof(float), 256);
   float *pytab = (float *)p;
   p += align_up((size_t)H * sizeof(float), 256);
+  if (attrs.pxy_out) {   // the caller keeps the tables (the workspace's stay unused)
+    pxtab = attrs.pxy_out;
+    pytab = attrs.pxy_out + W;
+  }
   const int edge = region_edge(B, W, H), cell = kCellRegions * edge;
   const int cells_x = (W + cell - 1) / cell, cells_y = (H + cell - 1) / cell;
   const int cells_per_image = cells_x * cells_y;
@@ -2158,7 +2205,7 @@ int launch_render_forward_l1(const float *vertices, const float *transforms, con
                              int L, float *clip, int32_t *ids, float *bary, float *z, int want_z, float *rgba,
                              uint8_t *rgba_u8, void *corner_records, void *backward_prepared, uint8_t *empty_regions, void *ws,
                              const float *target, const uint8_t *target_empty, float *loss, uint8_t *signs, float *partials,
-                             hipStream_t s) {
+                             hipStream_t s, bool private_gbuffer) {
   if (target && (size_t)B * W * H == 0) {
     if (zero_async(loss, sizeof(float), s) != hipSuccess) return check_launch();
   }
@@ -2189,6 +2236,11 @@ int launch_render_forward_l1(const float *vertices, const float *transforms, con
     shade.l1_signs = signs;
     shade.l1_partials = partials;
     shade.l1_inv_n = 1.0f / (float)((size_t)B * H * W * 4);
+    if (private_gbuffer) {   // (mr_render_forward_l1_private has checked: target and backward_prepared given, bary unused)
+      shade.no_bary = true;
+      setup.edge_recs = (EdgeRec *)((char *)backward_prepared + fold_private_edges_offset(B, T));
+      setup.pxy_out = (float *)((char *)backward_prepared + fold_private_tables_offset(B, T));
+    }
   }
   const int rc = raster_forward(clip, tris, B, V, T, W, H, ids, bary, z, shade, setup, ws, s);
   if (rc != MR_OK || !target) return rc;

@@ -517,10 +517,15 @@ struct ShadeFoldLaneFn : ShadeGradFn<L, SIGNS, false> {
   }
   __device__ __forceinline__ void accumulate(const typename Base::Pixel &p, const Triangle &t, float (&a)[kN],
                                              typename Base::Image &im) const {
+    accumulate_at(p.b, p.g, t, a, im);
+  }
+  // the pixel's contribution from its barycentrics pb and upstream gradient pg (also ShadeFoldLaneNoBaryFn's)
+  __device__ __forceinline__ void accumulate_at(const F3 &pb, const F3 &pg, const FoldTriangleW &t, float (&a)[kN],
+                                                typename Base::Image &im) const {
     float at[9], dat[9];
 #pragma unroll
-    for (int k = 0; k < 9; ++k) at[k] = fmaf(p.b.x, t.e0[k], fmaf(p.b.y, t.e1[k], t.c2[k]));
-    Base::template attribute_gradients<kUnscaled>(at, p.g, im, dat);
+    for (int k = 0; k < 9; ++k) at[k] = fmaf(pb.x, t.e0[k], fmaf(pb.y, t.e1[k], t.c2[k]));
+    Base::template attribute_gradients<kUnscaled>(at, pg, im, dat);
     float g0 = 0.f, g1 = 0.f;
 #pragma unroll
     for (int k = 0; k < 9; ++k) {
@@ -529,15 +534,102 @@ struct ShadeFoldLaneFn : ShadeGradFn<L, SIGNS, false> {
     }
     // the rasterizer's backward, pulled back to world space per TRIANGLE (corner_rec.h: store_fold_record):
     //   y = d L / d position attribute + (g0 b0 + g1 b1) S + g0 P0 + g1 P1
-    const float h = fmaf(g0, p.b.x, g1 * p.b.y);
+    const float h = fmaf(g0, pb.x, g1 * pb.y);
     float y[3];
 #pragma unroll
     for (int c = 0; c < 3; ++c) y[c] = fmaf(h, t.S[c], fmaf(g0, t.P0[c], fmaf(g1, t.P1[c], dat[3 + c])));
-    const float b[3] = {p.b.x, p.b.y, p.b.z};
+    const float b[3] = {pb.x, pb.y, pb.z};
 #pragma unroll
     for (int k = 0; k < 3; ++k)
 #pragma unroll
       for (int c = 0; c < 3; ++c) a[k * 3 + c] = fmaf(b[k], y[c], a[k * 3 + c]);
+  }
+};
+
+// ShadeFoldLaneFn<L, true> over the PRIVATE G-buffer of mr_render_forward_l1_private: no barycentric plane.  fetch()
+// loads the id and the sign codes only (5 B/px instead of 17); a covered pixel's barycentrics are rebuilt from its
+// centre (the rasterizer's own tables, kept in the private block) and its triangle's sign-corrected adjugate (EdgeRec)
+// with the expression the forward's depth loop evaluates -- every product and sum rounded once, then the correctly
+// rounded quotients (raster_forward.hip: div3_common_denominator; cpp:384-387) -- so they have the bits the plane
+// would have held.  Background is id -1 (the forward stores what it carries); the rule of ShadeGradFn::prepare, a
+// barycentric sum that is not positive contributes nothing, is applied to the rebuilt values.
+#ifndef MR_FOLD_NOBARY_DIV
+#define MR_FOLD_NOBARY_DIV 1   // 1: the ordinary division, the forward's own quotient (0.2364-0.2397 ms); 0: e * rcp(s), round 5's form, not
+                               // bit-identical (0.2270-0.2288).  (The forward's rcp refinement with the division as its fallback: 0.2334-0.2343.)
+#endif
+#ifndef MR_FOLD_NOBARY_WAVES
+#define MR_FOLD_NOBARY_WAVES 4   // 105-111 VGPRs without spills (the nine edge coefficients ride with the triangle's record); bound to 5
+                                 // waves the allocator spills 19-27 registers and the kernel takes 0.397 ms instead of 0.239 (same box)
+#endif
+template <int L>
+struct ShadeFoldLaneNoBaryFn : ShadeFoldLaneFn<L, true> {
+  using Fold = ShadeFoldLaneFn<L, true>;
+  using Base = typename Fold::Base;
+  static_assert(L >= 1, "lights in registers");
+  static constexpr int kMinWavesPerSimd = MR_FOLD_NOBARY_WAVES;
+  const EdgeRec *__restrict__ edge_recs;
+  const float *__restrict__ pxtab, *__restrict__ pytab;
+  struct Raw {
+    int t;
+    unsigned code;
+    float px, py;
+  };
+  struct Pixel {
+    F3 g;
+    float px, py;
+    int tri;
+  };
+  struct Triangle : FoldTriangleW {
+    float m[9];
+  };
+  __device__ __forceinline__ void fetch(int img, int x, int y, size_t pix, Raw &r) const {
+    (void)pix;
+    const size_t img_px = (size_t)img * this->H * this->W;                         // wave-uniform (ShadeGradFn::fetch)
+    const unsigned gpix = (unsigned)(y * this->W) + (unsigned)x;                   // G-buffer row y
+    const unsigned ipix = (unsigned)((this->H - 1 - y) * this->W) + (unsigned)x;   // image row (un-flipped)
+    r.t = __builtin_nontemporal_load((const int32_t *)((const char *)(this->ids + img_px) + gpix * 4u));
+    r.code = __builtin_nontemporal_load(this->signs + img_px + ipix);
+    r.px = pxtab[x];   // (the lane's column does not change down the strip; the row's value is wave-uniform)
+    r.py = pytab[y];
+  }
+  __device__ __forceinline__ bool prepare(const Raw &r, int T, int &tri, Pixel &p) const {
+    if ((unsigned)r.t >= (unsigned)T) return false;   // -1: background
+    p.g.x = (float)(int)__builtin_amdgcn_sbfe(r.code, 0u, 2u);
+    p.g.y = (float)(int)__builtin_amdgcn_sbfe(r.code, 2u, 2u);
+    p.g.z = (float)(int)__builtin_amdgcn_sbfe(r.code, 4u, 2u);
+    p.px = r.px;
+    p.py = r.py;
+    p.tri = r.t;
+    tri = r.t;
+    return true;
+  }
+  __device__ __forceinline__ void load_triangle(int img, int tri, Triangle &t) const {
+    load_fold_triangle_w(this->fold_recs + (size_t)img * this->T_ + tri, t);
+    const EdgeRec *e = edge_recs + (size_t)img * this->T_ + tri;
+    const float4 q0 = e->q[0], q1 = e->q[1], q2 = e->q[2];
+    t.m[0] = q0.x; t.m[1] = q0.y; t.m[2] = q0.z; t.m[3] = q0.w;
+    t.m[4] = q1.x; t.m[5] = q1.y; t.m[6] = q1.z; t.m[7] = q1.w;
+    t.m[8] = q2.x;
+  }
+  __device__ __forceinline__ void accumulate(const Pixel &p, const Triangle &t, float (&a)[Fold::kN],
+                                             typename Base::Image &im) const {
+    F3 b;
+    {
+#pragma clang fp contract(off)
+      const float e0 = (t.m[0] * p.px + t.m[1] * p.py) + t.m[2];
+      const float e1 = (t.m[3] * p.px + t.m[4] * p.py) + t.m[5];
+      const float e2 = (t.m[6] * p.px + t.m[7] * p.py) + t.m[8];
+      const float sum = (e0 + e1) + e2;
+#if MR_FOLD_NOBARY_DIV == 1
+      b.x = e0 / sum; b.y = e1 / sum; b.z = e2 / sum;
+#else
+      const float r = __builtin_amdgcn_rcpf(sum);
+      b.x = e0 * r; b.y = e1 * r; b.z = e2 * r;
+#endif
+    }
+    const float pre = (2.0f * b.x + 2.0f * b.y) + 2.0f * b.z;
+    if (!(pre > 0.0f)) return;
+    Fold::accumulate_at(b, p.g, t, a, im);
   }
 };
 
@@ -830,6 +922,7 @@ int launch_shade_forward(const int32_t *ids, const float *bary, const float *nor
 }
 
 size_t shade_backward_prepared_bytes(int B, int T) { return fold_prepared_bytes(B, T); }
+size_t shade_backward_private_bytes(int B, int T, int W, int H) { return fold_private_bytes(B, T, W, H); }
 
 thread_local int g_deterministic = 0;  // mr_set_deterministic
 // mr_debug_set_shade_backward_kernel: 0 = automatic (lane-accumulating kernel where it exists: no
@@ -863,6 +956,7 @@ struct ShadeBackwardCase {
   bool light_grads, normals, diffuse, clip;      // gradients wanted (positions: always)
   bool transforms, adjacency, records, prepared; // optional inputs given
   bool normalised;                               // MR_GBUFFER_NORMALISED
+  bool private_gbuffer;                          // MR_GBUFFER_PRIVATE: no barycentric plane, ids -1 on background
   bool deterministic;
   int kernel;                                    // mr_debug_set_shade_backward_kernel
   bool nonempty;                                 // T > 0 && V > 0
@@ -876,6 +970,7 @@ struct ShadeBackwardPlan {
   bool opaque = false, folded = false, LG = false;   // OPAQUE (ShadeLaneFn), FOLD (ShadeDiffLaneFn), light gradients
   bool fused_clear = false;        // k_bwd_setup clears the accumulator rows and light_grads, the gather writes every output once
   bool use_prepared = false;       // records and cleared rows come from mr_render_forward's block: no setup launch
+  bool no_bary = false;            // ShadeFoldLaneNoBaryFn: barycentrics rebuilt from the private block's edge records
   bool dclip_scratch = false;      // the clip-space sums are formed, but land in the workspace
   ShadeVertexPass vertex = ShadeVertexPass::kNone;
 };
@@ -911,6 +1006,10 @@ ShadeBackwardPlan plan_shade_backward(const ShadeBackwardCase &c) {
   p.dclip_scratch = !c.clip && !fold;
   p.fused_clear = c.adjacency && !c.deterministic;   // (always the case with `fold`: transforms imply the adjacency)
   p.use_prepared = fold_diff && c.prepared && MR_SHADE_USE_PREPARED;
+  // The private G-buffer of mr_render_forward_l1_private: one kernel reads it -- the folded lane kernel on sign codes
+  // with its lights in registers, fed by that call's block.
+  p.no_bary = c.private_gbuffer;
+  if (c.private_gbuffer && !(p.use_prepared && c.signs && p.NL >= 1 && c.kernel != 1)) return rejected();
   p.opaque = c.normalised && !c.light_grads;
   p.pixel = diff ? ShadePixelPass::kDiffLanes : fold_diff ? ShadePixelPass::kFoldLanes
           : lanes ? ShadePixelPass::kLanes : ShadePixelPass::kRows;
@@ -936,6 +1035,8 @@ struct ShadePixelArgs {
   const FoldRec *fold_recs;
   float *acc;
   const DetBlock *det;       // the deterministic mode's block (rows kernel only), or nullptr
+  const EdgeRec *edge_recs = nullptr;   // these three: the private block's tail (plan.no_bary)
+  const float *pxtab = nullptr, *pytab = nullptr;
 };
 template <int NL, bool SIGNS, bool LG>
 ShadeGradFn<NL, SIGNS, LG> shade_grad_fn(const ShadePixelArgs &a, bool diff_basis) {
@@ -961,6 +1062,13 @@ int launch_shade_pixels_of(const ShadeBackwardPlan &plan, const ShadePixelArgs &
       break;
     case ShadePixelPass::kFoldLanes:
       if constexpr (!LG) {
+        if constexpr (SIGNS && NL >= 1) {
+          if (plan.no_bary) {
+            const ShadeFoldLaneNoBaryFn<NL> fn{{shade_grad_fn<NL, true, false>(a, true), a.fold_recs}, a.edge_recs, a.pxtab, a.pytab};
+            return launch_shade_lanes(fn, a, s);
+          }
+        }
+        if (plan.no_bary) break;
         const ShadeFoldLaneFn<NL, SIGNS> fn{shade_grad_fn<NL, SIGNS, false>(a, true), a.fold_recs};
         return launch_shade_lanes(fn, a, s);
       }
@@ -1024,7 +1132,8 @@ int launch_shade_backward(const float *drgba, const uint8_t *signs, const float 
   const ShadeBackwardPlan plan = plan_shade_backward(
       {L, signs != nullptr, light_grads != nullptr, dnormals != nullptr, ddiffuse != nullptr, dclip != nullptr,
        transforms != nullptr, vertex_offsets && vertex_entries, corner_records != nullptr, prepared != nullptr,
-       (gbuffer_flags & MR_GBUFFER_NORMALISED) != 0, det, g_shade_backward_kernel, T > 0 && V > 0});
+       (gbuffer_flags & MR_GBUFFER_NORMALISED) != 0, (gbuffer_flags & MR_GBUFFER_PRIVATE) != 0, det, g_shade_backward_kernel,
+       T > 0 && V > 0});
   if (plan.rc != MR_OK) return plan.rc;
   const ShadeBackwardLayout at = shade_backward_layout(B, V, T, W, H);
   char *const base = (char *)ws;
@@ -1093,9 +1202,15 @@ int launch_shade_backward(const float *drgba, const uint8_t *signs, const float 
   }
   {
     KernelTimer timer(MR_TIMER_SHADE_BACKWARD, s);
-    rc = launch_shade_pixels(plan, {drgba, signs, sign_upstream, sign_inv_n, ids, bary, corners, recs,
-                                    Lights{light_pos, light_col, ambient, L}, light_rows, B, T, W, H, transforms,
-                                    empty_regions, fold_recs, acc, det ? det_block : nullptr}, s);
+    ShadePixelArgs pixel_args{drgba, signs, sign_upstream, sign_inv_n, ids, bary, corners, recs,
+                              Lights{light_pos, light_col, ambient, L}, light_rows, B, T, W, H, transforms,
+                              empty_regions, fold_recs, acc, det ? det_block : nullptr};
+    if (plan.no_bary) {
+      pixel_args.edge_recs = (const EdgeRec *)((const char *)prepared + fold_private_edges_offset(B, T));
+      pixel_args.pxtab = (const float *)((const char *)prepared + fold_private_tables_offset(B, T));
+      pixel_args.pytab = pixel_args.pxtab + W;
+    }
+    rc = launch_shade_pixels(plan, pixel_args, s);
   }
   if (rc != MR_OK) return rc;
   if (light_grads) {  // the strips' rows of light sums -> [B][6L + 3], fixed order (every element is written)

@@ -132,10 +132,18 @@ class FusedAttributeRasterizer(torch.autograd.Function):
 #   loss_in_forward(False)   the one-pass forward does NOT compute mean|image - target| for a remembered target
 #                            (losses.remember_target): the loss kernel reads the image back, as it does for any other
 #                            target.  For A/B runs and the parity tests.
-# Defaults come from the environment (MR_SHADING_EPILOGUE, MR_EMIT_UINT8_FRAMES, MR_LOSS_IN_FORWARD) once, at import.
+#   private_gbuffer(False)   the loss-in-forward route keeps the public G-buffer (ids 0 on background, barycentric
+#                            plane) even when only the vertices require grad.  On (the default) that route writes no
+#                            barycentric plane: the backward's lane kernel rebuilds them (mr_render_forward_l1_private),
+#                            and whoever needs the public G-buffer after all -- a second backward over a retained graph,
+#                            a dense image gradient -- gets it from one plain rasterizer pass over the saved inputs.
+#                            For A/B runs and the parity tests.
+# Defaults come from the environment (MR_SHADING_EPILOGUE, MR_EMIT_UINT8_FRAMES, MR_LOSS_IN_FORWARD, MR_PRIVATE_GBUFFER)
+# once, at import.
 _DEFAULTS = {"shading_epilogue": os.environ.get("MR_SHADING_EPILOGUE", "1") != "0",
              "emit_uint8_frames": os.environ.get("MR_EMIT_UINT8_FRAMES", "0") != "0",
-             "loss_in_forward": os.environ.get("MR_LOSS_IN_FORWARD", "1") != "0"}
+             "loss_in_forward": os.environ.get("MR_LOSS_IN_FORWARD", "1") != "0",
+             "private_gbuffer": os.environ.get("MR_PRIVATE_GBUFFER", "1") != "0"}
 _scoped = threading.local()
 
 
@@ -169,6 +177,11 @@ def emit_uint8_frames(on):
 def loss_in_forward(on):
     """with loss_in_forward(False): image = render(...) -- see the comment above."""
     return _scoped_switch("loss_in_forward", on)
+
+
+def private_gbuffer(on):
+    """with private_gbuffer(False): image = render(...) -- see the comment above."""
+    return _scoped_switch("private_gbuffer", on)
 
 
 PREPARE_BACKWARD = True   # False: the backward always runs its own setup kernel (A/B, tests)
@@ -212,16 +225,22 @@ class FusedPhongRenderer(torch.autograd.Function):
         ctx.l1_in_forward = None
         if epilogue and any(needs) and _switch("loss_in_forward"):
             l1_target, l1_map = _remembered_target(verts.device, (verts.shape[0], int(image_height), int(image_width), 4))
+        # Both decisions taken -- the loss comes out of this pass and only the vertices require grad -- the G-buffer has one
+        # reader, this node's own backward through the sign codes: it is written without its barycentric plane, with -1
+        # for background (see private_gbuffer above; one to four lights: the kernel that reads it keeps them in registers).
+        private = bool(prepare and l1_target is not None and _switch("private_gbuffer") and lp.shape[1] <= 4)
         if epilogue:
             out = _native.render_forward(
                 verts, xf, args[0], args[1], triangles, lp, li, amb, int(image_width), int(image_height),
                 want_z=False, want_u8=bool(want_frames), prepare_backward=prepare, want_empty_regions=EMPTY_REGIONS,
                 l1_target=l1_target.detach() if l1_target is not None else None,
-                l1_target_empty=l1_map if EMPTY_REGIONS else None)
+                l1_target_empty=l1_map if EMPTY_REGIONS else None, private_gbuffer=private)
             if l1_target is not None:
                 ctx.l1_in_forward = {"target_key": _target_key(l1_target), "loss": out[-1][0], "signs": out[-1][1]}
                 out = out[:-1]
             clip, ids, bary, _, rgba, corner_records = out[:6]
+            if private:   # (a placeholder in the saved list; _input_grads never hands it on)
+                bary = torch.empty(0, dtype=torch.float32, device=verts.device)
             if want_frames:
                 frames = out[6]
             if EMPTY_REGIONS:   # which 64 x 64 blocks of the image are known to be empty (the loss and the backward skip them)
@@ -245,7 +264,9 @@ class FusedPhongRenderer(torch.autograd.Function):
         # the prepared block serves ONE backward call (its accumulator rows are left dirty): a second backward over
         # a retained graph -- through this node or through FusedPhongL1Loss, which shares this dict -- runs the
         # backward's own setup kernel instead
-        ctx.prepared_state = {"used": prepared is None}
+        # "private": ids / bary above are the private G-buffer; "public": the (ids, bary) of the plain rasterizer pass that
+        # replaced them, once somebody needed it (_input_grads)
+        ctx.prepared_state = {"used": prepared is None, "private": bool(epilogue and private), "public": None}
         ctx.empty_regions = empty_regions
         if frames is not None:
             ctx.mark_non_differentiable(frames)
@@ -268,6 +289,21 @@ class FusedPhongRenderer(torch.autograd.Function):
         use_prepared = prepared.numel() > 0 and prepared_state is not None and not prepared_state["used"]
         if use_prepared:
             prepared_state["used"] = True
+        private = False
+        if prepared_state is not None and prepared_state.get("private"):
+            # The private G-buffer serves the call it was written for: the first backward, through the sign codes, to the
+            # vertices alone, on the lane kernel.  Anything else reads the public one -- the plain rasterizer pass on the
+            # saved clip-space vertices, the same kernel and deterministic: the ids and barycentrics the fused forward
+            # would have stored -- made once and kept.  (The private block begins with the public one: it still serves.)
+            private = (use_prepared and l1_signs is not None and prepared_state["public"] is None
+                       and not (needs_transform_grad or needs_light_grads or needs_normal_grad or needs_diffuse_grad)
+                       and not _native.deterministic() and _native._shade_backward_kernel != 1)
+            if private:
+                bary = None
+            else:
+                if prepared_state["public"] is None:
+                    prepared_state["public"] = _native.rasterize_forward(clip, triangles, ids.shape[2], ids.shape[1])[:2]
+                ids, bary = prepared_state["public"]
         dclip, dn, dverts, dd, dlp, dli, damb = _native.shade_backward(
             upstream, ids, bary, clip, normals, verts, diffuse, triangles, lp, li, amb,
             corner_records=corner_records, adjacency=(offsets, entries), l1_signs=l1_signs, transforms=xf,
@@ -275,7 +311,8 @@ class FusedPhongRenderer(torch.autograd.Function):
             want_diffuse_grads=needs_diffuse_grad,
             want_clip_grads=needs_transform_grad,   # d clip on its own only feeds d transforms below
             prepared=prepared if use_prepared else None, empty_regions=empty_regions,
-            normalised_gbuffer=True)   # this function's own forward wrote ids / bary
+            normalised_gbuffer=True,   # this function's own forward wrote ids / bary
+            private_gbuffer=private)
         dxf = None
         if needs_transform_grad:  # d clip[b,v,r] / d xf[b,r,k] = (vertex, 1)[k]
             ones = torch.ones(verts.shape[0], verts.shape[1], 1, dtype=verts.dtype, device=verts.device)
