@@ -848,6 +848,53 @@ int mr_nearest_triangle_backward(const float *points, const float *vertices, con
                                  const float *grad_points, const float *grad_images, float *dpoints, float *dvertices,
                                  void *stream);
 
+/* ---- triangle to nearest point: the mesh-to-point distance (no reference counterpart) ----
+ * The other direction of the search above, with the same pair arithmetic: dist^2(p, t) of a (point, triangle) pair is
+ * the same float32 number in both.  Per image b, for every triangle t of the shared topology, over the points p_j
+ * with j < lengths[b] ("Point-cloud losses"):
+ *   sqdist_t = min_j dist^2(p_j, triangle t)   from the CLOSED triangle, dist^2 as defined above
+ *   index_t  = the LOWEST j that attains it (equal float32 distances), whatever the launch shape
+ *   bary_t   = the barycentrics of the triangle's closest point c_t to p_index_t, >= 0
+ * A triangle with an index outside [0, V), and a triangle for which no point compared below +inf (lengths[b] = 0,
+ * NaN coordinates, a point at +-inf), get sqdist 0, index -1, bary 0; every other index lies in [0, lengths[b]).
+ *   points [B,N,3], vertices [B,V,3] f32;  triangles [T,3] i32;  lengths [B] i32 (device) or NULL = all N
+ *   sqdist [B,T] f32 out or NULL;  index [B,T] i32 out;  bary [B,T,3] f32 out
+ *   usable [B] i32 out or NULL: U, the triangles with every index in [0, V) (the same for every image), counted on
+ *          the device; needed with total, and by the backward of the mean
+ *   total  [B] f32 out or NULL: the sum of sqdist over image b's triangles / U in a fixed order (a usable triangle
+ *          without a result adds 0 and counts); 0 when U = 0 or the image has no valid point
+ * mr_nearest_point_of_triangle_plan: the launch shape, a pure host function: one triangle a lane, `workgroup_size`
+ * triangles a workgroup; the cloud is cut into `splits` runs of whole `point_tile`s, which meet through 64-bit keys
+ * (distance bits << 32) | point index as in mr_nearest_forward; `points_per_step` is 2 where the points are visited
+ * as packed fp32 pairs.  The workspace holds the per-image triangle records (80 bytes each), those keys and the
+ * partial sums; 16-byte aligned, needed by every call.
+ *
+ * mr_nearest_point_of_triangle_backward: the gradient of  sum_t g_t sqdist_t  with the barycentrics held constant:
+ *   dvertices_k = -sum 2 g_t bary_tk (p_index_t - c_t)  over the corners that name vertex k,
+ *   dpoints_j   =  sum_{t: index_t = j} 2 g_t (p_j - c_t);
+ *   g_t = grad_triangles[b,t] ([B,T]) or grad_images[b] / usable[b] ([B], the mean's upstream): exactly one.
+ *   corner_order [B,3T], corner_offsets [B,V+1] i32: the inverted index of the entries 3 t + k keyed by the vertex
+ *         triangles[t][k] (-1 for triangles without a result); needed when dvertices is asked for
+ *   point_order [B,T], point_offsets [B,N+1] i32: the inverted index of index (triangles grouped by the point they
+ *         chose); needed when dpoints is asked for.  Both as for mr_nearest_backward: a stable sort, -1 last.
+ *   dpoints [B,N,3], dvertices [B,V,3] f32 out or NULL (not computed); each is written completely, rows that nobody
+ *         names 0
+ * No atomics, no zero-fills, bit-reproducible in either deterministic mode.  Limits as for mr_nearest_triangle_*. */
+int mr_nearest_point_of_triangle_plan(int B, int N, int T, int *splits, int *points_per_step, int *point_tile,
+                                      int *workgroup_size);
+size_t mr_nearest_point_of_triangle_workspace_bytes(int B, int N, int T);
+int mr_nearest_point_of_triangle_forward(const float *points, const float *vertices, const int32_t *triangles,
+                                         const int32_t *lengths, int B, int N, int V, int T, float *sqdist,
+                                         int32_t *index, float *bary, float *total, int32_t *usable, void *workspace,
+                                         size_t workspace_bytes, void *stream);
+int mr_nearest_point_of_triangle_backward(const float *points, const float *vertices, const int32_t *triangles,
+                                          const int32_t *lengths, int B, int N, int V, int T, const int32_t *index,
+                                          const float *bary, const int32_t *corner_order,
+                                          const int32_t *corner_offsets, const int32_t *point_order,
+                                          const int32_t *point_offsets, const float *grad_triangles,
+                                          const float *grad_images, const int32_t *usable, float *dpoints,
+                                          float *dvertices, void *stream);
+
 /* ---- clip-space transforms --------------------------------------------------------------
  * perspective(aspect, fov_y, near, far) . look_at(eye, center, up) per image, the product render() and
  * rasterize() apply to the vertices (src/common/camera_utils.py:45-139; src/mesh_renderer/render.py

@@ -366,6 +366,18 @@ def lib():
         except AttributeError as e:   # the point-to-mesh entry points came without an ABI version bump
             raise NativeLibraryError("%s lacks the nearest-triangle entry points (%s): rebuild it (make -C "
                                      "pytorch_mesh_renderer_amd/csrc)" % (LIB_PATH, e))
+        try:
+            L.mr_nearest_point_of_triangle_plan.argtypes = [ci] * 3 + [vp] * 4
+            L.mr_nearest_point_of_triangle_plan.restype = ci
+            L.mr_nearest_point_of_triangle_workspace_bytes.argtypes = [ci] * 3
+            L.mr_nearest_point_of_triangle_workspace_bytes.restype = sz
+            L.mr_nearest_point_of_triangle_forward.argtypes = [vp] * 4 + [ci] * 4 + [vp] * 6 + [sz, vp]
+            L.mr_nearest_point_of_triangle_forward.restype = ci
+            L.mr_nearest_point_of_triangle_backward.argtypes = [vp] * 4 + [ci] * 4 + [vp] * 12
+            L.mr_nearest_point_of_triangle_backward.restype = ci
+        except AttributeError as e:   # the mesh-to-point entry points came without an ABI version bump
+            raise NativeLibraryError("%s lacks the nearest-point-of-triangle entry points (%s): rebuild it (make -C "
+                                     "pytorch_mesh_renderer_amd/csrc)" % (LIB_PATH, e))
         _lib = L
     return _lib
 
@@ -1214,6 +1226,86 @@ def nearest_triangle_backward(points, vertices, triangles, lengths, face, bary, 
         rc = L.mr_nearest_triangle_backward(*[_ptr(t) for t in held[:4]], B, N, V, T, *[_ptr(t) for t in held[4:]],
                                             _ptr(dpoints), _ptr(dvertices), _stream(dev))
     _check(rc, "mr_nearest_triangle_backward")
+    return dpoints, dvertices
+
+
+def nearest_point_of_triangle_plan(B, N, T):
+    """The launch shape mr_nearest_point_of_triangle_forward takes for B images of T triangles against N points, a
+    pure host function: {"splits", "points_per_step", "point_tile", "workgroup_size"} (include/mesh_raster.h)."""
+    out = (ctypes.c_int * 4)()
+    rc = lib().mr_nearest_point_of_triangle_plan(int(B), int(N), int(T),
+                                                 *[ctypes.c_void_p(ctypes.addressof(out) + 4 * k) for k in range(4)])
+    if rc != MR_OK:
+        raise ValueError("nearest_point_of_triangle_plan takes 1..65535 images of 1..2^28 points and triangles, got "
+                         "(%r, %r, %r)" % (B, N, T))
+    return dict(zip(("splits", "points_per_step", "point_tile", "workgroup_size"), list(out)))
+
+
+def nearest_point_of_triangle_forward(points, vertices, triangles, lengths=None, want_sqdist=True, want_total=False):
+    """points [B,N,3], vertices [B,V,3] f32, triangles [T,3] i32, lengths [B] i32 or None (device) -> (sqdist [B,T]
+    f32 or None, index [B,T] i32, bary [B,T,3] f32, total [B] f32 or None: the mean of sqdist over the usable
+    triangles, usable [B] i32 or None: their count, formed on the device): mr_nearest_point_of_triangle_forward."""
+    B, N, V, T = _chk_point_mesh(points, vertices, triangles, lengths)
+    dev = _require_device(points, vertices, triangles, *([lengths] if lengths is not None else []))
+    L = lib()
+    points, vertices, triangles = points.contiguous(), vertices.contiguous(), triangles.contiguous()
+    lengths = lengths.contiguous() if lengths is not None else None
+    sqdist = torch.empty(B, T, dtype=_F32, device=dev) if want_sqdist else None
+    index = torch.empty(B, T, dtype=_I32, device=dev)
+    bary = torch.empty(B, T, 3, dtype=_F32, device=dev)
+    total = torch.empty(B, dtype=_F32, device=dev) if want_total else None
+    usable = torch.empty(B, dtype=_I32, device=dev) if want_total else None
+    with torch.cuda.device(dev):
+        ws, have = _workspace(dev, L.mr_nearest_point_of_triangle_workspace_bytes(B, N, T))
+        rc = L.mr_nearest_point_of_triangle_forward(_ptr(points), _ptr(vertices), _ptr(triangles), _ptr(lengths), B, N,
+                                                    V, T, _ptr(sqdist), _ptr(index), _ptr(bary), _ptr(total),
+                                                    _ptr(usable), _ptr(ws), have, _stream(dev))
+    _check(rc, "mr_nearest_point_of_triangle_forward")
+    return sqdist, index, bary, total, usable
+
+
+def nearest_point_of_triangle_backward(points, vertices, triangles, lengths, index, bary, corner_index=None,
+                                       point_index=None, grad_triangles=None, grad_images=None, usable=None,
+                                       want_dpoints=True, want_dvertices=True):
+    """mr_nearest_point_of_triangle_backward -> (dpoints [B,N,3] or None, dvertices [B,V,3] or None).  corner_index:
+    (order [B,3T], offsets [B,V+1]), nearest_inverted_index() of the (triangle, corner) entries' vertices, needed for
+    dvertices; point_index: (order [B,T], offsets [B,N+1]), that of index, needed for dpoints; usable [B] i32: the
+    forward's count, needed with grad_images."""
+    B, N, V, T = _chk_point_mesh(points, vertices, triangles, lengths)
+    _chk("index", index, _I32, B, T)
+    _chk("bary", bary, _F32, B, T, 3)
+    tensors = [points, vertices, triangles, index, bary] + ([lengths] if lengths is not None else [])
+    if corner_index is not None:
+        _chk("corner order", corner_index[0], _I32, B, 3 * T)
+        _chk("corner offsets", corner_index[1], _I32, B, V + 1)
+        tensors += list(corner_index)
+    if point_index is not None:
+        _chk("point order", point_index[0], _I32, B, T)
+        _chk("point offsets", point_index[1], _I32, B, N + 1)
+        tensors += list(point_index)
+    if grad_triangles is not None:
+        _chk("upstream gradient", grad_triangles, _F32, B, T)
+        tensors.append(grad_triangles)
+    if grad_images is not None:
+        _chk("upstream gradient", grad_images, _F32, B)
+        tensors.append(grad_images)
+    if usable is not None:
+        _chk("usable", usable, _I32, B)
+        tensors.append(usable)
+    dev = _require_device(*tensors)
+    L = lib()
+    c = lambda t: t.contiguous() if t is not None else None
+    corner_order, corner_offsets = corner_index if corner_index is not None else (None, None)
+    point_order, point_offsets = point_index if point_index is not None else (None, None)
+    dpoints = torch.empty(B, N, 3, dtype=_F32, device=dev) if want_dpoints else None
+    dvertices = torch.empty(B, V, 3, dtype=_F32, device=dev) if want_dvertices else None
+    held = [c(t) for t in (points, vertices, triangles, lengths, index, bary, corner_order, corner_offsets, point_order,
+                           point_offsets, grad_triangles, grad_images, usable)]
+    with torch.cuda.device(dev):
+        rc = L.mr_nearest_point_of_triangle_backward(*[_ptr(t) for t in held[:4]], B, N, V, T,
+                                                     *[_ptr(t) for t in held[4:]], _ptr(dpoints), _ptr(dvertices),
+                                                     _stream(dev))
+    _check(rc, "mr_nearest_point_of_triangle_backward")
     return dpoints, dvertices
 
 

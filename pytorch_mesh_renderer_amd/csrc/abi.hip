@@ -963,6 +963,52 @@ int mr_nearest_triangle_backward(const float *points, const float *vertices, con
                                               (hipStream_t)stream);
 }
 
+int mr_nearest_point_of_triangle_plan(int B, int N, int T, int *splits, int *points_per_step, int *point_tile,
+                                      int *workgroup_size) {
+  if (bad_nearest_dims(B, N, T) || !splits || !points_per_step || !point_tile || !workgroup_size) return MR_EINVAL;
+  mr::nearest_point_of_triangle_plan(B, N, T, splits, points_per_step, point_tile, workgroup_size);
+  return MR_OK;
+}
+
+size_t mr_nearest_point_of_triangle_workspace_bytes(int B, int N, int T) {
+  if (bad_nearest_dims(B, N, T)) return 0;
+  return mr::nearest_point_of_triangle_ws(B, N, T);
+}
+
+int mr_nearest_point_of_triangle_forward(const float *points, const float *vertices, const int32_t *triangles,
+                                         const int32_t *lengths, int B, int N, int V, int T, float *sqdist,
+                                         int32_t *index, float *bary, float *total, int32_t *usable, void *workspace,
+                                         size_t workspace_bytes, void *stream) {
+  if (bad_nearest_triangle_dims(B, N, V, T)) return MR_EINVAL;
+  if (!points || !vertices || !triangles || !index || !bary) return MR_EINVAL;
+  if (total && !usable) return MR_EINVAL;   // the mean's divisor is formed on the device
+  const int rc = check_ws(workspace, workspace_bytes, mr::nearest_point_of_triangle_ws(B, N, T));
+  if (rc != MR_OK) return rc;
+  if (misaligned(workspace, 16)) return MR_EINVAL;   // the records are read as 16-byte words
+  return mr::launch_nearest_point_of_triangle_forward(points, vertices, triangles, lengths, B, N, V, T, sqdist, index,
+                                                      bary, total, usable, workspace, (hipStream_t)stream);
+}
+
+int mr_nearest_point_of_triangle_backward(const float *points, const float *vertices, const int32_t *triangles,
+                                          const int32_t *lengths, int B, int N, int V, int T, const int32_t *index,
+                                          const float *bary, const int32_t *corner_order,
+                                          const int32_t *corner_offsets, const int32_t *point_order,
+                                          const int32_t *point_offsets, const float *grad_triangles,
+                                          const float *grad_images, const int32_t *usable, float *dpoints,
+                                          float *dvertices, void *stream) {
+  if (bad_nearest_triangle_dims(B, N, V, T)) return MR_EINVAL;
+  if (!points || !vertices || !triangles || !index || !bary) return MR_EINVAL;
+  if ((grad_triangles != nullptr) == (grad_images != nullptr)) return MR_EINVAL;   // exactly one upstream
+  if (grad_images && !usable) return MR_EINVAL;                   // the mean's upstream is divided by the count
+  if ((corner_order == nullptr) != (corner_offsets == nullptr) || (point_order == nullptr) != (point_offsets == nullptr))
+    return MR_EINVAL;
+  if ((dvertices && !corner_order) || (dpoints && !point_order)) return MR_EINVAL;   // both are gathers over an index
+  return mr::launch_nearest_point_of_triangle_backward(points, vertices, triangles, lengths, B, N, V, T, index, bary,
+                                                       corner_order, corner_offsets, point_order, point_offsets,
+                                                       grad_triangles, grad_images, usable, dpoints, dvertices,
+                                                       (hipStream_t)stream);
+}
+
 int mr_texture_forward(const float *tex, const float *uv, const float *mask, int tex_batched, int Ht, int Wt, int C,
                        int B, int W, int H, int boundary, float *out, void *stream) {
   if (bad_texture_dims(tex_batched, Ht, Wt, C, B, W, H) || bad_boundary(boundary)) return MR_EINVAL;

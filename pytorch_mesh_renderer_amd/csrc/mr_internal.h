@@ -282,6 +282,21 @@ int launch_nearest_triangle_backward(const float *points, const float *vertices,
                                      const float *bary, const int32_t *order, const int32_t *offsets,
                                      const float *grad_points, const float *grad_images, float *dpoints,
                                      float *dvertices, hipStream_t s);
+// triangle to nearest point, mr_nearest_point_of_triangle_* (nearest.hip)
+void nearest_point_of_triangle_plan(int B, int N, int T, int *splits, int *points_per_step, int *point_tile,
+                                    int *workgroup);
+size_t nearest_point_of_triangle_ws(int B, int N, int T);
+int launch_nearest_point_of_triangle_forward(const float *points, const float *vertices, const int32_t *triangles,
+                                             const int32_t *lengths, int B, int N, int V, int T, float *sqdist,
+                                             int32_t *index, float *bary, float *total, int32_t *usable, void *ws,
+                                             hipStream_t s);
+int launch_nearest_point_of_triangle_backward(const float *points, const float *vertices, const int32_t *triangles,
+                                              const int32_t *lengths, int B, int N, int V, int T,
+                                              const int32_t *index, const float *bary, const int32_t *corner_order,
+                                              const int32_t *corner_offsets, const int32_t *point_order,
+                                              const int32_t *point_offsets, const float *grad_triangles,
+                                              const float *grad_images, const int32_t *usable, float *dpoints,
+                                              float *dvertices, hipStream_t s);
 
 // spherical-harmonics shading (sh_shade.hip)
 size_t sh_shade_backward_ws(int B, int W, int H);

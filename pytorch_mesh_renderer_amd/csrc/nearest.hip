@@ -1,6 +1,7 @@
 // Brute-force nearest neighbour between two point clouds on gfx950, the hot path of the Chamfer distance
 // (mr_nearest_forward / _backward; semantics: INTEGRATION.md, "Point-cloud losses"), and further down the same search
-// from points to the triangles of a mesh (mr_nearest_triangle_forward / _backward: "point to triangle").
+// from points to the triangles of a mesh (mr_nearest_triangle_forward / _backward: "point to triangle") and, last,
+// from the triangles to the points (mr_nearest_point_of_triangle_forward / _backward: "triangle to point").
 //
 // Per image b, for every query x_i (i < x_lengths[b]) over the targets y_j (j < y_lengths[b]):
 //   sqdist_i = min_j (x_i - y_j).(x_i - y_j),   idx_i = the lowest j that attains it
@@ -93,6 +94,13 @@ __device__ __forceinline__ float block_sum(float v) {
   if (lane_id() == 0) part[(int)threadIdx.x / kWave] = v;
   __syncthreads();
   return (part[0] + part[1]) + (part[2] + part[3]);
+}
+
+// The sum of v over the eight lanes that own one destination row, in a fixed butterfly, on each of them.
+__device__ __forceinline__ float group_sum(float v) {
+#pragma unroll
+  for (int m = 1; m < kLanesPerPoint; m <<= 1) v += __shfl_xor(v, m, kLanesPerPoint);
+  return v;
 }
 
 constexpr unsigned long long kNoKey = ~0ull;
@@ -309,12 +317,7 @@ __global__ __launch_bounds__(kThreads) void k_nearest_backward(
       }
     }
   }
-#pragma unroll
-  for (int m = 1; m < kLanesPerPoint; m <<= 1) {
-    dx += __shfl_xor(dx, m, kLanesPerPoint);
-    dy += __shfl_xor(dy, m, kLanesPerPoint);
-    dz += __shfl_xor(dz, m, kLanesPerPoint);
-  }
+  dx = group_sum(dx), dy = group_sum(dy), dz = group_sum(dz);
   if (have && sub == 0) dp[(size_t)b * Np + p] = V3{dx, dy, dz};
 }
 
@@ -511,6 +514,21 @@ __global__ __launch_bounds__(kThreads) void k_nt_search(const float *__restrict_
   }
 }
 
+// One chosen (point, record) pair once more, with the searches' own functions: its distance -- the number that won,
+// bit for bit -- and the barycentrics of the candidate that gave it.  False when no candidate compares below +inf.
+__device__ __forceinline__ bool nt_evaluate(V3 p, const float4 *__restrict__ r, float &d, V3 &w) {
+  const Candidates<float> c = tri_candidates<float>(p.x, p.y, p.z, r[0], r[1], r[2], r[3], r[4]);
+  d = tri_distance(c);
+  // the same chain as tri_distance, remembering whose parameters won
+  float best = INFINITY, beta = 0.0f, gamma = 0.0f;
+  if (c.inside < best) best = c.inside, beta = c.v, gamma = c.w;
+  if (c.ab < best) best = c.ab, beta = c.tab, gamma = 0.0f;
+  if (c.bc < best) best = c.bc, beta = 1.0f - c.tbc, gamma = c.tbc;
+  if (c.ca < best) best = c.ca, beta = 0.0f, gamma = c.tca;
+  w = V3{fmaxf(1.0f - (beta + gamma), 0.0f), beta, gamma};
+  return d < INFINITY;
+}
+
 // The chosen face once more, with the search's own functions -> sqdist, the face (-1 for a row without a result),
 // the barycentrics and the workgroup's partial sum.  grid (ceil(N / kThreads), B)
 __global__ __launch_bounds__(kThreads) void k_nt_finish(const V3 *__restrict__ points,
@@ -527,18 +545,8 @@ __global__ __launch_bounds__(kThreads) void k_nt_finish(const V3 *__restrict__ p
     int f = i < nv ? face[row] : -1;
     V3 w = {0.0f, 0.0f, 0.0f};
     if ((unsigned)f < (unsigned)T) {
-      const V3 p = points[row];
-      const float4 *r = records + ((size_t)b * T + f) * kRecWords;
-      const Candidates<float> c = tri_candidates<float>(p.x, p.y, p.z, r[0], r[1], r[2], r[3], r[4]);
-      d = tri_distance(c);
-      // the same chain as tri_distance, remembering whose parameters won
-      float best = INFINITY, beta = 0.0f, gamma = 0.0f;
-      if (c.inside < best) best = c.inside, beta = c.v, gamma = c.w;
-      if (c.ab < best) best = c.ab, beta = c.tab, gamma = 0.0f;
-      if (c.bc < best) best = c.bc, beta = 1.0f - c.tbc, gamma = c.tbc;
-      if (c.ca < best) best = c.ca, beta = 0.0f, gamma = c.tca;
-      w = V3{fmaxf(1.0f - (beta + gamma), 0.0f), beta, gamma};
-      if (!(d < INFINITY)) f = -1;   // (the search never names such a face)
+      if (!nt_evaluate(points[row], records + ((size_t)b * T + f) * kRecWords, d, w))
+        f = -1;   // (the search never names such a face)
     } else {
       f = -1;
     }
@@ -556,15 +564,26 @@ __global__ __launch_bounds__(kThreads) void k_nt_finish(const V3 *__restrict__ p
   }
 }
 
-// p_i - c_i = d - (beta e0 + gamma e1) of query i and its weights; false for a row without a face.
+// p - c = d - (beta e0 + gamma e1) of the pair that row i of a saved result names, and the row's weights.  Point to
+// triangle: the rows are the points, row i pairs point i with the face chosen[i].  Triangle to point
+// (kRowsAreTriangles, i < T): the rows are the triangles, row i pairs triangle i with the point chosen[i].  pv: the
+// image's valid points.  False for a row without a result.
+template <bool kRowsAreTriangles>
 __device__ __forceinline__ bool nt_residual(const V3 *__restrict__ pb, const V3 *__restrict__ vb,
-                                            const int32_t *__restrict__ triangles, const int32_t *__restrict__ fb,
-                                            const V3 *__restrict__ wb, int i, int V, int T, V3 &r, V3 &w) {
-  const int f = fb[i];
-  if ((unsigned)f >= (unsigned)T) return false;
+                                            const int32_t *__restrict__ triangles, const int32_t *__restrict__ cb,
+                                            const V3 *__restrict__ wb, int i, int pv, int V, int T, V3 &r, V3 &w) {
+  int point = i, f = i;
+  if constexpr (kRowsAreTriangles) {
+    point = cb[i];
+    if ((unsigned)point >= (unsigned)pv) return false;
+  } else {
+    if (i >= pv) return false;
+    f = cb[i];
+    if ((unsigned)f >= (unsigned)T) return false;
+  }
   const int ia = triangles[3 * (size_t)f], ib = triangles[3 * (size_t)f + 1], ic = triangles[3 * (size_t)f + 2];
   if ((unsigned)ia >= (unsigned)V || (unsigned)ib >= (unsigned)V || (unsigned)ic >= (unsigned)V) return false;
-  const V3 p = pb[i], a = vb[ia], e = vb[ib], c = vb[ic];
+  const V3 p = pb[point], a = vb[ia], e = vb[ib], c = vb[ic];
   w = wb[i];
   r.x = (p.x - a.x) - (w.y * (e.x - a.x) + w.z * (c.x - a.x));
   r.y = (p.y - a.y) - (w.y * (e.y - a.y) + w.z * (c.y - a.y));
@@ -584,57 +603,235 @@ __global__ __launch_bounds__(kThreads) void k_nt_backward_points(
   const int nv = valid_count(lengths, b, N);
   const Upstream up{g_points, (g_images && nv > 0) ? g_images[b] / (float)nv : 0.0f};
   V3 out = {0.0f, 0.0f, 0.0f}, r, w;
-  if (i < nv && nt_residual(points + (size_t)b * N, vertices + (size_t)b * V, triangles, face + (size_t)b * N,
-                            bary + (size_t)b * N, i, V, T, r, w)) {
+  if (nt_residual<false>(points + (size_t)b * N, vertices + (size_t)b * V, triangles, face + (size_t)b * N,
+                         bary + (size_t)b * N, i, nv, V, T, r, w)) {
     const float g2 = 2.0f * up.at((size_t)b * N + i);
     out = V3{g2 * r.x, g2 * r.y, g2 * r.z};
   }
   dpoints[(size_t)b * N + i] = out;
 }
 
-// dvertices[b, v] = -sum over the (query, corner) entries that name v of 2 g_i bary_ik (p_i - c_i): order [B, 3N]
-// holds the entries 3 i + k grouped by vertex, each group ascending, offsets [B, V + 1].  Eight lanes per vertex.
-// grid (ceil(V / kPointsPerBlock), B)
+// dvertices[b, v] = -sum over the (row, corner) entries that name v of 2 g_i bary_ik (p - c)_i: with R rows (the N
+// points, or with kRowsAreTriangles the T triangles: nt_residual) order [B, 3R] holds the entries 3 i + k grouped by
+// vertex, each group ascending, offsets [B, V + 1]; chosen, bary and g_rows are [B, R, ...].  The mean's upstream is
+// g_images[b] over the image's valid points, with triangle rows over divisors[b] (its usable triangles).  Eight
+// lanes per vertex.  grid (ceil(V / kPointsPerBlock), B)
+template <bool kRowsAreTriangles>
 __global__ __launch_bounds__(kThreads) void k_nt_backward_vertices(
     const V3 *__restrict__ points, const V3 *__restrict__ vertices, const int32_t *__restrict__ triangles,
-    const int32_t *__restrict__ lengths, int N, int V, int T, const int32_t *__restrict__ face,
+    const int32_t *__restrict__ lengths, int N, int V, int T, const int32_t *__restrict__ chosen,
     const V3 *__restrict__ bary, const int32_t *__restrict__ order, const int32_t *__restrict__ offsets,
-    const float *__restrict__ g_points, const float *__restrict__ g_images, V3 *__restrict__ dvertices) {
+    const float *__restrict__ g_rows, const float *__restrict__ g_images, const int32_t *__restrict__ divisors,
+    V3 *__restrict__ dvertices) {
   const int b = (int)blockIdx.y;
   const int v = (int)blockIdx.x * kPointsPerBlock + (int)threadIdx.x / kLanesPerPoint;
   const int sub = (int)threadIdx.x % kLanesPerPoint;
   const bool have = v < V;   // (whole groups of eight: the butterfly below stays inside one)
+  const int R = kRowsAreTriangles ? T : N;
   const int nv = valid_count(lengths, b, N);
-  const Upstream up{g_points, (g_images && nv > 0) ? g_images[b] / (float)nv : 0.0f};
+  const int count = kRowsAreTriangles ? (g_images ? divisors[b] : 0) : nv;
+  const Upstream up{g_rows, (g_images && count > 0) ? g_images[b] / (float)count : 0.0f};
   float dx = 0.0f, dy = 0.0f, dz = 0.0f;
   if (have) {
     const int32_t *off = offsets + (size_t)b * (V + 1);
-    const int e0 = max(off[v], 0), e1 = min(off[v + 1], 3 * N);
+    const int e0 = max(off[v], 0), e1 = min(off[v + 1], 3 * R);
     for (int k = e0 + sub; k < e1; k += kLanesPerPoint) {
-      const int e = order[(size_t)b * 3 * N + k];
-      if ((unsigned)e >= (unsigned)(3 * N)) continue;
+      const int e = order[(size_t)b * 3 * R + k];
+      if ((unsigned)e >= (unsigned)(3 * R)) continue;
       const int i = e / 3, corner = e - 3 * i;
       V3 r, w;
-      if (i >= nv || !nt_residual(points + (size_t)b * N, vertices + (size_t)b * V, triangles, face + (size_t)b * N,
-                                  bary + (size_t)b * N, i, V, T, r, w))
+      if (!nt_residual<kRowsAreTriangles>(points + (size_t)b * N, vertices + (size_t)b * V, triangles,
+                                          chosen + (size_t)b * R, bary + (size_t)b * R, i, nv, V, T, r, w))
         continue;
-      const float s = -2.0f * up.at((size_t)b * N + i) * (corner == 0 ? w.x : (corner == 1 ? w.y : w.z));
+      const float s = -2.0f * up.at((size_t)b * R + i) * (corner == 0 ? w.x : (corner == 1 ? w.y : w.z));
       dx += s * r.x;
       dy += s * r.y;
       dz += s * r.z;
     }
   }
-#pragma unroll
-  for (int m = 1; m < kLanesPerPoint; m <<= 1) {
-    dx += __shfl_xor(dx, m, kLanesPerPoint);
-    dy += __shfl_xor(dy, m, kLanesPerPoint);
-    dz += __shfl_xor(dz, m, kLanesPerPoint);
-  }
+  dx = group_sum(dx), dy = group_sum(dy), dz = group_sum(dz);
   if (have && sub == 0) dvertices[(size_t)b * V + v] = V3{dx, dy, dz};
+}
+
+// ---- triangle to point ------------------------------------------------------------------------------------------
+// mr_nearest_point_of_triangle_forward / _backward: per image, for every triangle the squared distance from the
+// CLOSED triangle to the nearest valid point of the cloud, the lowest point that attains it and the barycentrics of
+// the triangle's closest point to it ("Point-cloud losses").  The pair arithmetic is the one above
+// (k_nt_setup's records, tri_candidates / tri_distance), so a (point, triangle) pair has the same float32 distance in
+// both directions.  The roles are exchanged: a lane keeps ONE triangle's record in registers (20 of them, loaded
+// once), a workgroup stages 256 of the image's valid points at a time in LDS as three planes and every lane reads
+// the same point (one address for the wavefront: a broadcast) -- or the same two, points j and j + 1 in the halves
+// of a packed pair against the record broadcast into both.  Ascending points and a strict '<' (inside a pair the
+// lower half first), so the lowest point of equal distances wins; NaN and +inf never do; an odd last point shares
+// its pair with a +inf point written into the tile.  The grid is (triangle blocks, splits, B): plan_of with the
+// triangles as the queries cuts the CLOUD into `splits` runs of whole tiles, which meet through the 64-bit keys and
+// k_nearest_merge.  k_tp_finish is k_nt_finish for triangle rows (nt_evaluate), the mean is k_nearest_mean over its
+// partial sums with the divisor k_tp_usable counted: the usable triangles, a property of the topology.
+//
+// Backward: dv_k = -sum 2 g_t bary_tk (p_j(t) - c_t) is k_nt_backward_vertices with triangle rows, a gather over
+// the inverted index of the 3T (triangle, corner) entries keyed by vertex; dp_j = sum_{t: index_t = j} 2 g_t
+// (p_j - c_t) is a gather over the inverted index of the triangles keyed by the point they chose.
+constexpr int kPointTile = 256;        // points staged in LDS at a time (3 KB), and the granularity of a split
+constexpr int kPackedFrom = kPointTile;   // clouds of at least a tile are searched two points a step
+static_assert(kPointTile % 2 == 0, "an odd count is padded to a pair inside the tile");
+
+// U, the triangles with every index in [0, V), into counts[0 .. B).  One workgroup.
+__global__ __launch_bounds__(kThreads) void k_tp_usable(const int32_t *__restrict__ triangles, int V, int T, int B,
+                                                        int32_t *__restrict__ counts) {
+  __shared__ int part[kThreads / kWave];
+  int n = 0;
+  for (int t = (int)threadIdx.x; t < T; t += kThreads) {
+    const int ia = triangles[3 * (size_t)t], ib = triangles[3 * (size_t)t + 1], ic = triangles[3 * (size_t)t + 2];
+    n += ((unsigned)ia < (unsigned)V && (unsigned)ib < (unsigned)V && (unsigned)ic < (unsigned)V) ? 1 : 0;
+  }
+#pragma unroll
+  for (int m = 1; m < kWave; m <<= 1) n += __shfl_xor(n, m, kWave);
+  if (lane_id() == 0) part[(int)threadIdx.x / kWave] = n;
+  __syncthreads();
+  const int total = (part[0] + part[1]) + (part[2] + part[3]);
+  for (int b = (int)threadIdx.x; b < B; b += kThreads) counts[b] = total;
+}
+
+// grid (triangle blocks, splits, B).  keys != null (splits > 1): one key per (image, split, triangle) for
+// k_nearest_merge; keys == null: the point, -1 for a triangle no point compared below +inf for.
+template <typename F>
+__global__ __launch_bounds__(kThreads) void k_tp_search(const float *__restrict__ points,
+                                                        const float4 *__restrict__ records,
+                                                        const int32_t *__restrict__ lengths, int N, int T, int chunk,
+                                                        int32_t *__restrict__ index,
+                                                        unsigned long long *__restrict__ keys) {
+  constexpr int Q = (int)(sizeof(F) / sizeof(float));
+  __shared__ __attribute__((aligned(16))) float sx[kPointTile];
+  __shared__ __attribute__((aligned(16))) float sy[kPointTile];
+  __shared__ __attribute__((aligned(16))) float sz[kPointTile];
+  const int b = (int)blockIdx.z, split = (int)blockIdx.y;
+  const int nv = valid_count(lengths, b, N);
+  const float *pb = points + (size_t)b * N * 3;
+  const int j0 = min(split * chunk, nv), j1 = min(j0 + chunk, nv);   // this split's points, maybe none
+  const int t = (int)blockIdx.x * kThreads + (int)threadIdx.x;
+
+  // a lane beyond T keeps an unusable triangle's record: nothing compares below +inf
+  float4 r0 = make_float4(INFINITY, INFINITY, INFINITY, 0.0f);
+  float4 r1 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), r2 = r1, r3 = r1, r4 = r1;
+  if (t < T) {
+    const float4 *r = records + ((size_t)b * T + t) * kRecWords;
+    r0 = r[0], r1 = r[1], r2 = r[2], r3 = r[3], r4 = r[4];
+  }
+  float best = INFINITY;
+  int bi = -1;
+
+  for (int t0 = j0; t0 < j1; t0 += kPointTile) {   // j0, j1: the same on every thread
+    const int count = min(kPointTile, j1 - t0);
+    const int padded = (count + Q - 1) / Q * Q;   // <= kPointTile; +inf beyond count: never nearer than anything
+    __syncthreads();
+    for (int f = (int)threadIdx.x; f < 3 * padded; f += kThreads) {
+      const int j = f / 3, c = f - 3 * j;
+      const float v = j < count ? pb[3 * (size_t)t0 + f] : INFINITY;
+      float *plane = c == 0 ? sx : (c == 1 ? sy : sz);
+      plane[j] = v;
+    }
+    __syncthreads();
+    for (int j = 0; j < padded; j += Q) {
+      F px, py, pz;   // one address for the wavefront
+      if constexpr (Q == 2) {
+        const float2 x = *reinterpret_cast<const float2 *>(&sx[j]);
+        const float2 y = *reinterpret_cast<const float2 *>(&sy[j]);
+        const float2 z = *reinterpret_cast<const float2 *>(&sz[j]);
+        px = F{x.x, x.y}, py = F{y.x, y.y}, pz = F{z.x, z.y};
+      } else {
+        px = sx[j], py = sy[j], pz = sz[j];
+      }
+      const F d = tri_distance(tri_candidates<F>(px, py, pz, r0, r1, r2, r3, r4));
+#pragma unroll
+      for (int q = 0; q < Q; ++q) {
+        const float dq = part_of(d, q);
+        if (dq < best) {   // strict, points ascending: the lowest point of equal distances; NaN and +inf never win
+          best = dq;
+          bi = t0 + j + q;
+        }
+      }
+    }
+  }
+
+  if (t >= T) return;
+  if (keys)
+    keys[((size_t)b * gridDim.y + split) * T + t] =
+        bi >= 0 ? ((unsigned long long)__float_as_uint(best) << 32) | (unsigned)bi : kNoKey;
+  else
+    index[(size_t)b * T + t] = bi;
+}
+
+// The chosen point once more, with the search's own functions -> sqdist, the point (-1 for a triangle without a
+// result), the barycentrics and the workgroup's partial sum.  grid (ceil(T / kThreads), B)
+__global__ __launch_bounds__(kThreads) void k_tp_finish(const V3 *__restrict__ points,
+                                                        const float4 *__restrict__ records,
+                                                        const int32_t *__restrict__ lengths, int N, int T,
+                                                        float *__restrict__ sqdist, int32_t *__restrict__ index,
+                                                        V3 *__restrict__ bary, float *__restrict__ partials) {
+  const int b = (int)blockIdx.y;
+  const int t = (int)blockIdx.x * kThreads + (int)threadIdx.x;
+  const int nv = valid_count(lengths, b, N);
+  float d = 0.0f;
+  if (t < T) {
+    const size_t row = (size_t)b * T + t;
+    int j = index[row];
+    V3 w = {0.0f, 0.0f, 0.0f};
+    if ((unsigned)j >= (unsigned)nv || !nt_evaluate(points[(size_t)b * N + j], records + row * kRecWords, d, w)) {
+      j = -1;   // (the search never names such a point)
+      d = 0.0f;
+      w = V3{0.0f, 0.0f, 0.0f};
+    }
+    if (sqdist) sqdist[row] = d;
+    index[row] = j;
+    bary[row] = w;
+  }
+  if (partials) {   // (a kernel argument: the same on every thread)
+    d = block_sum(d);
+    if (threadIdx.x == 0) partials[(size_t)b * gridDim.x + blockIdx.x] = d;
+  }
+}
+
+// dpoints[b, j] = sum over the triangles t that chose point j of 2 g_t (p_j - c_t): order [B, T] holds the triangles
+// grouped by their point, each group ascending, offsets [B, N + 1].  A point nobody chose, and a padded one, get 0.
+// Eight lanes per point.  grid (ceil(N / kPointsPerBlock), B)
+__global__ __launch_bounds__(kThreads) void k_tp_backward_points(
+    const V3 *__restrict__ points, const V3 *__restrict__ vertices, const int32_t *__restrict__ triangles,
+    const int32_t *__restrict__ lengths, int N, int V, int T, const int32_t *__restrict__ index,
+    const V3 *__restrict__ bary, const int32_t *__restrict__ order, const int32_t *__restrict__ offsets,
+    const float *__restrict__ g_triangles, const float *__restrict__ g_images, const int32_t *__restrict__ divisors,
+    V3 *__restrict__ dpoints) {
+  const int b = (int)blockIdx.y;
+  const int p = (int)blockIdx.x * kPointsPerBlock + (int)threadIdx.x / kLanesPerPoint;
+  const int sub = (int)threadIdx.x % kLanesPerPoint;
+  const bool have = p < N;   // (whole groups of eight: the butterfly below stays inside one)
+  const int nv = valid_count(lengths, b, N);
+  const int count = g_images ? divisors[b] : 0;
+  const Upstream up{g_triangles, (g_images && count > 0) ? g_images[b] / (float)count : 0.0f};
+  float dx = 0.0f, dy = 0.0f, dz = 0.0f;
+  if (have && p < nv) {
+    const int32_t *off = offsets + (size_t)b * (N + 1);
+    const int e0 = max(off[p], 0), e1 = min(off[p + 1], T);
+    for (int k = e0 + sub; k < e1; k += kLanesPerPoint) {
+      const int t = order[(size_t)b * T + k];
+      V3 r, w;
+      if ((unsigned)t >= (unsigned)T || index[(size_t)b * T + t] != p ||
+          !nt_residual<true>(points + (size_t)b * N, vertices + (size_t)b * V, triangles, index + (size_t)b * T,
+                             bary + (size_t)b * T, t, nv, V, T, r, w))
+        continue;
+      const float g2 = 2.0f * up.at((size_t)b * T + t);
+      dx += g2 * r.x;
+      dy += g2 * r.y;
+      dz += g2 * r.z;
+    }
+  }
+  dx = group_sum(dx), dy = group_sum(dy), dz = group_sum(dz);
+  if (have && sub == 0) dpoints[(size_t)b * N + p] = V3{dx, dy, dz};
 }
 
 inline Plan tri_plan_of(int B, int N, int T) { return plan_of(B, N, T, kTriTile, kTriWideQueries); }
 inline size_t tri_records_bytes(int B, int T) { return align_up((size_t)B * T * kRecWords * sizeof(float4), 256); }
+// triangle to point: the T triangles are the queries, one a lane, and the N points the targets that are split
+inline Plan point_plan_of(int B, int N, int T) { return plan_of(B, T, N, kPointTile, 1); }
 
 }  // namespace
 
@@ -772,9 +969,92 @@ int launch_nearest_triangle_backward(const float *points, const float *vertices,
   }
   if (dvertices) {
     const dim3 grid((unsigned)((V + kPointsPerBlock - 1) / kPointsPerBlock), (unsigned)B);
-    hipLaunchKernelGGL(k_nt_backward_vertices, grid, dim3(kThreads), 0, s, (const V3 *)points, (const V3 *)vertices,
-                       triangles, lengths, N, V, T, face, (const V3 *)bary, order, offsets, grad_points, grad_images,
-                       (V3 *)dvertices);
+    hipLaunchKernelGGL(k_nt_backward_vertices<false>, grid, dim3(kThreads), 0, s, (const V3 *)points,
+                       (const V3 *)vertices, triangles, lengths, N, V, T, face, (const V3 *)bary, order, offsets,
+                       grad_points, grad_images, (const int32_t *)nullptr, (V3 *)dvertices);
+    return check_launch();
+  }
+  return MR_OK;
+}
+
+void nearest_point_of_triangle_plan(int B, int N, int T, int *splits, int *points_per_step, int *point_tile,
+                                    int *workgroup) {
+  *splits = point_plan_of(B, N, T).splits;
+  *points_per_step = N >= kPackedFrom ? 2 : 1;
+  *point_tile = kPointTile;
+  *workgroup = kThreads;
+}
+
+// records | keys (splits > 1) | the finish pass's partial sums
+size_t nearest_point_of_triangle_ws(int B, int N, int T) {
+  const Plan p = point_plan_of(B, N, T);
+  return tri_records_bytes(B, T) + keys_bytes(p, B, T) + align_up((size_t)B * merge_blocks_of(T) * sizeof(float), 256);
+}
+
+int launch_nearest_point_of_triangle_forward(const float *points, const float *vertices, const int32_t *triangles,
+                                             const int32_t *lengths, int B, int N, int V, int T, float *sqdist,
+                                             int32_t *index, float *bary, float *total, int32_t *usable, void *ws,
+                                             hipStream_t s) {
+  const Plan p = point_plan_of(B, N, T);
+  float4 *records = (float4 *)ws;
+  unsigned long long *keys = p.splits > 1 ? (unsigned long long *)((char *)ws + tri_records_bytes(B, T)) : nullptr;
+  float *partials = total ? (float *)((char *)ws + tri_records_bytes(B, T) + keys_bytes(p, B, T)) : nullptr;
+  const dim3 rows(merge_blocks_of(T), (unsigned)B);
+  hipLaunchKernelGGL(k_nt_setup, rows, dim3(kThreads), 0, s, (const V3 *)vertices, triangles, V, T, records);
+  int rc = check_launch();
+  if (rc != MR_OK) return rc;
+  const dim3 grid((unsigned)p.query_blocks, (unsigned)p.splits, (unsigned)B);
+  if (N >= kPackedFrom)
+    hipLaunchKernelGGL(k_tp_search<F2>, grid, dim3(kThreads), 0, s, points, (const float4 *)records, lengths, N, T,
+                       p.chunk, index, keys);
+  else
+    hipLaunchKernelGGL(k_tp_search<float>, grid, dim3(kThreads), 0, s, points, (const float4 *)records, lengths, N, T,
+                       p.chunk, index, keys);
+  rc = check_launch();
+  if (rc != MR_OK) return rc;
+  if (keys) {   // the lowest key of a triangle's splits -> its point, -1 without one: every triangle row is a query
+    hipLaunchKernelGGL(k_nearest_merge, rows, dim3(kThreads), 0, s, (const unsigned long long *)keys, p.splits,
+                       (const int32_t *)nullptr, lengths, T, N, (float *)nullptr, index, (float *)nullptr);
+    rc = check_launch();
+    if (rc != MR_OK) return rc;
+  }
+  hipLaunchKernelGGL(k_tp_finish, rows, dim3(kThreads), 0, s, (const V3 *)points, (const float4 *)records, lengths, N,
+                     T, sqdist, index, (V3 *)bary, partials);
+  rc = check_launch();
+  if (rc != MR_OK) return rc;
+  if (usable) {
+    hipLaunchKernelGGL(k_tp_usable, dim3(1), dim3(kThreads), 0, s, triangles, V, T, B, usable);
+    rc = check_launch();
+    if (rc != MR_OK) return rc;
+  }
+  if (total) {   // the mean over the usable triangles; 0 without one or without a valid point
+    hipLaunchKernelGGL(k_nearest_mean, dim3((unsigned)B), dim3(kThreads), 0, s, (const float *)partials,
+                       (int)merge_blocks_of(T), (const int32_t *)usable, lengths, T, N, 1.0f, 0, total);
+    rc = check_launch();
+  }
+  return rc;
+}
+
+int launch_nearest_point_of_triangle_backward(const float *points, const float *vertices, const int32_t *triangles,
+                                              const int32_t *lengths, int B, int N, int V, int T,
+                                              const int32_t *index, const float *bary, const int32_t *corner_order,
+                                              const int32_t *corner_offsets, const int32_t *point_order,
+                                              const int32_t *point_offsets, const float *grad_triangles,
+                                              const float *grad_images, const int32_t *usable, float *dpoints,
+                                              float *dvertices, hipStream_t s) {
+  if (dpoints) {
+    const dim3 grid((unsigned)((N + kPointsPerBlock - 1) / kPointsPerBlock), (unsigned)B);
+    hipLaunchKernelGGL(k_tp_backward_points, grid, dim3(kThreads), 0, s, (const V3 *)points, (const V3 *)vertices,
+                       triangles, lengths, N, V, T, index, (const V3 *)bary, point_order, point_offsets, grad_triangles,
+                       grad_images, usable, (V3 *)dpoints);
+    const int rc = check_launch();
+    if (rc != MR_OK) return rc;
+  }
+  if (dvertices) {
+    const dim3 grid((unsigned)((V + kPointsPerBlock - 1) / kPointsPerBlock), (unsigned)B);
+    hipLaunchKernelGGL(k_nt_backward_vertices<true>, grid, dim3(kThreads), 0, s, (const V3 *)points,
+                       (const V3 *)vertices, triangles, lengths, N, V, T, index, (const V3 *)bary, corner_order,
+                       corner_offsets, grad_triangles, grad_images, usable, (V3 *)dvertices);
     return check_launch();
   }
   return MR_OK;

@@ -8,7 +8,8 @@ neighbours), bitwise reproducible in either deterministic mode.  Host tensors an
 data preparation, the CPU test-suite -- take the equivalent torch expression, chunked over the queries.
 Distances are always computed as (x - y).(x - y), never as |x|^2 + |y|^2 - 2 x.y.  nearest_triangles and
 point_mesh_distance measure to the mesh's surface itself -- the nearest closed triangle -- with kernels of the same
-file and the same split between the HIP and the torch path.
+file and the same split between the HIP and the torch path; triangle_nearest_points and mesh_point_distance are the
+other direction, every triangle against its nearest point, and point_mesh_face_distance is the sum of the two means.
 """
 import torch
 from torch.autograd.function import once_differentiable
@@ -461,3 +462,125 @@ def point_mesh_distance(points, vertices, triangles, lengths=None):
     else:
         total = _mean_torch(_nearest_triangles_torch(p, v, tris, lengths)[0], lengths, None)
     return total[0] if single else total
+
+
+# ---- mesh to point: the nearest point of every triangle -------------------------------------------------------------
+
+def _triangle_nearest_points_torch(points, v, tris, lengths):
+    """triangle_nearest_points as a torch expression on the device and in the dtype of points [B,N,3] / v [B,V,3]:
+    the point is searched chunk by chunk of triangles without a graph; the distance from the triangle's closest point
+    to it, the barycentrics held constant (the envelope theorem), is then an ordinary differentiable expression."""
+    B, N, _ = points.shape
+    T = tris.shape[0]
+    dev = points.device
+    n_valid = lengths.long() if lengths is not None else torch.full((B,), N, dtype=torch.int64, device=dev)
+    with torch.no_grad():
+        records = _TriangleRecords(v.detach(), tris)
+        outside = torch.arange(N, device=dev)[None, None, :] >= n_valid[:, None, None]          # [B,1,N]
+        cloud = points.detach()[:, None, :, :]                                                   # [B,1,N,3]
+        rows = max(1, _CHUNK_BYTES // max(1, B * N * 12 * points.element_size()))
+        chosen, found = [], []
+        for start in range(0, T, rows):
+            some = records.select(lambda t: t[:, start:start + rows, None])      # [B,rows,1,...]
+            dist, _, _ = _triangle_candidates(cloud, some)
+            best = dist.min(dim=-1).values.masked_fill(outside, float("inf"))    # [B,rows,N]
+            nearest = best.min(dim=2)                                             # the first of equal minima
+            chosen.append(nearest.indices)
+            found.append(nearest.values < float("inf"))
+        valid = torch.cat(found, dim=1) & records.usable[None, :]
+        index = torch.where(valid, torch.cat(chosen, dim=1), torch.zeros((), dtype=torch.int64, device=dev))
+        take = index[..., None].expand(-1, -1, 3)                                 # [B,T,3]
+        dist, beta, gamma = _triangle_candidates(torch.gather(points.detach(), 1, take), records.select(lambda t: t))
+        which = dist.min(dim=-1).indices[..., None]
+        beta, gamma = torch.gather(beta, -1, which)[..., 0], torch.gather(gamma, -1, which)[..., 0]
+        bary = torch.stack([(1.0 - (beta + gamma)).clamp(min=0), beta, gamma], -1)
+        bary = torch.where(valid[..., None], bary, torch.zeros_like(bary))
+    # differentiable: |d - (beta e0 + gamma e1)|^2 with d = p_index - a
+    corner = tris.clamp(0, v.shape[1] - 1)
+    a, b, c = (v.index_select(1, corner[:, k]) for k in range(3))
+    residual = (torch.gather(points, 1, take) - a) - (bary[..., 1:2] * (b - a) + bary[..., 2:3] * (c - a))
+    residual = torch.where(valid[..., None], residual, torch.zeros_like(residual))   # no result: value 0, gradient 0
+    index = torch.where(valid, index, torch.full_like(index, -1))
+    return (residual * residual).sum(-1), index.to(torch.int32), bary, records.usable.sum()
+
+
+class _TriangleNearestPoints(torch.autograd.Function):
+    """Both public functions on the HIP path.  reduce False: (sqdist [B,T], index [B,T], bary [B,T,3]); reduce True:
+    the mean of sqdist over the usable triangles [B]."""
+
+    @staticmethod
+    def forward(ctx, points, vertices, triangles, lengths, reduce):
+        pd, vd = points.detach().contiguous(), vertices.detach().contiguous()
+        sqdist, index, bary, total, usable = _native.nearest_point_of_triangle_forward(
+            pd, vd, triangles, lengths, want_sqdist=not reduce, want_total=reduce)
+        ctx.reduce = reduce
+        ctx.save_for_backward(pd, vd, triangles, lengths, index, bary, usable)
+        if reduce:
+            return total
+        ctx.mark_non_differentiable(index, bary)
+        return sqdist, index, bary
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad, _index=None, _bary=None):
+        points, vertices, triangles, lengths, index, bary, usable = ctx.saved_tensors
+        want_dp, want_dv = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        none = (None,) * 3
+        if not (want_dp or want_dv):
+            return (None, None) + none
+        corner_index = point_index = None
+        if want_dv:   # the (triangle, corner) entries keyed by the vertex they name, -1 for triangles without a point
+            named = torch.where(index[..., None] < 0, torch.full_like(triangles, -1)[None], triangles[None])
+            corner_index = _native.nearest_inverted_index(named.reshape(index.shape[0], -1), vertices.shape[1])
+        if want_dp:   # the triangles keyed by the point they chose
+            point_index = _native.nearest_inverted_index(index, points.shape[1])
+        grad = grad.contiguous()
+        dp, dv = _native.nearest_point_of_triangle_backward(
+            points, vertices, triangles, lengths, index, bary, corner_index, point_index,
+            grad_triangles=None if ctx.reduce else grad, grad_images=grad if ctx.reduce else None, usable=usable,
+            want_dpoints=want_dp, want_dvertices=want_dv)
+        return (dp, dv) + none
+
+
+def triangle_nearest_points(points, vertices, triangles, lengths=None):
+    """points [B,N,3], vertices [B,V,3] (or [N,3], [V,3]: one image, results without the batch axis), triangles [T,3]
+    of any integer dtype (one topology for the batch) -> (sqdist [B,T], index [B,T] int32, bary [B,T,3]): for every
+    triangle the squared Euclidean distance from the CLOSED triangle (interior, edges and corners) to the nearest
+    valid point of its image, the lowest point index that attains it and the barycentrics of the triangle's closest
+    point to that point (>= 0, adding up to 1).  The other direction of nearest_triangles, with the same arithmetic
+    per (point, triangle) pair.  A zero-area triangle counts as its edges or its point.
+
+    sqdist is differentiable in points and vertices with the barycentrics held constant (the envelope theorem);
+    index and bary are not differentiable.  lengths: an optional integer [B] tensor on the points' device for padded
+    clouds, clamped to [0, N] on the device; padded rows influence nothing.  A triangle with an index outside [0, V),
+    and a triangle for which no point compared below +inf (lengths[b] = 0, NaN coordinates, a point at +-inf), get
+    sqdist 0, index -1, bary 0 and no gradient.  Every other index lies in [0, lengths[b])."""
+    p, v, tris, lengths, single = _point_mesh_arguments(points, vertices, triangles, lengths)
+    if _on_hip_path(p):
+        out = _TriangleNearestPoints.apply(p, v, _device_triangles(tris, v.shape[1]), lengths, False)
+    else:
+        out = _triangle_nearest_points_torch(p, v, tris, lengths)[:3]
+    return tuple(t[0] for t in out) if single else tuple(out)
+
+
+def mesh_point_distance(points, vertices, triangles, lengths=None):
+    """The mean over the usable triangles (every index in [0, V): a property of the topology, the same count U for
+    every image, formed on the device) of triangle_nearest_points' sqdist -> [B] (a 0-dim tensor without the batch
+    axis); 0 where U = 0 or the image has no valid point; a usable triangle without a result adds 0 and counts.
+    The mesh -> scan half of the exact data term: it keeps parts of the mesh that no scan point is near from being
+    ignored, without sampling the surface.  A fixed-order sum on a HIP device; differentiable in points and vertices,
+    and a gradient that is not required is not computed."""
+    p, v, tris, lengths, single = _point_mesh_arguments(points, vertices, triangles, lengths)
+    if _on_hip_path(p):
+        total = _TriangleNearestPoints.apply(p, v, _device_triangles(tris, v.shape[1]), lengths, True)
+    else:
+        sqdist, _, _, usable = _triangle_nearest_points_torch(p, v, tris, lengths)
+        total = sqdist.sum(1) / usable.clamp(min=1).to(sqdist.dtype)
+    return total[0] if single else total
+
+
+def point_mesh_face_distance(points, vertices, triangles, lengths=None):
+    """point_mesh_distance(...) + mesh_point_distance(...): both directions of the exact distance between a scan and
+    a mesh under PyTorch3D's name, each a mean of its own (over the valid points, over the usable triangles)."""
+    return (point_mesh_distance(points, vertices, triangles, lengths)
+            + mesh_point_distance(points, vertices, triangles, lengths))
