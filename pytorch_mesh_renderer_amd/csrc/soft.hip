@@ -29,6 +29,8 @@
 // Parity bar: 1e-4 abs on RGBA and gradients.  At the reference's default gamma = 1e-4 one ulp
 // of depth moves a logit by ~1e-3, so depth follows the reference's operation order; the 3x3
 // inverse is analytic here (torch's is LU), which was measured to cost ~2.5e-5 on RGB.
+// Per tensor and relative to its largest element, image and gradients also stay within 8x the error the float32
+// restatement itself has against a float64 evaluation (1e-7 .. 4e-5), scene by scene: tests/test_soft_truth_gpu.py.
 #include "corner_rec.h"
 
 namespace mr {
@@ -148,11 +150,12 @@ struct LightSet {
 
 __device__ __forceinline__ void edge_nearest(float px, float py, float ax, float ay, float abx, float aby, float nx,
                                              float ny, float ilen, float &t, float &d2) {  // rasterize.py:169-176
-  const float dpn = (px - ax) * nx + (py - ay) * ny;
+#pragma clang fp contract(off)  // see eval_pair: the fused operations are the ones written as fmaf
+  const float dpn = fmaf(px - ax, nx, (py - ay) * ny);
   const float prx = dpn * nx, pry = dpn * ny;
-  t = fminf(fmaxf((prx * nx + pry * ny) * ilen, 0.0f), 1.0f);
-  const float qx = ax + t * abx - px, qy = ay + t * aby - py;
-  d2 = qx * qx + qy * qy;
+  t = fminf(fmaxf(fmaf(prx, nx, pry * ny) * ilen, 0.0f), 1.0f);
+  const float qx = fmaf(t, abx, ax) - px, qy = fmaf(t, aby, ay) - py;
+  d2 = fmaf(qx, qx, qy * qy);
 }
 
 // mr_debug_soft_nearest (mesh_raster_debug.h): the two device functions above on caller-given points and
@@ -171,13 +174,22 @@ __global__ __launch_bounds__(kThreads) void k_debug_soft_nearest(const float2 *_
 }
 
 // Returns false when the pair is culled (bbox, blur radius, depth range).
+//
+// The backward recomputes the pair and takes exp(logit - m) against the max logit m the FORWARD stored, so both
+// kernels must round every operation on the way to the depth alike: at gamma = 1e-4 one ulp of sb . zn moves the
+// logit by 3e-4.  Left to the compiler they did not -- which multiplies are fused into an fma is decided after the
+// SLP vectoriser has packed the arithmetic around them, differently in the two kernels -- and the backward's softmax
+// weights were off by up to 9e-4 relative on the default parameters (tests/test_soft_truth_gpu.py, sphere-default:
+// 131x the float32 restatement's own error on the light intensity gradient, 78x on the diffuse one).  Contraction
+// is therefore off in this function and in edge_nearest; the fused operations are the ones written as fmaf.
 template <int ML>
 __device__ __forceinline__ bool eval_pair(const SoftRec &r, const CornerRec *__restrict__ corner_rec, Corners &cr,
                                           const LightSet<ML> &ls,
                                           const SoftParams &pr, float px, float py, Pair &o) {
+#pragma clang fp contract(off)
   if (!(px <= r.hi[0] && px >= r.lo[0] && py <= r.hi[1] && py >= r.lo[1])) return false;  // quadtree.py:18-31
 #pragma unroll
-  for (int i = 0; i < 3; ++i) o.bc[i] = r.minv[3 * i] * px + r.minv[3 * i + 1] * py + r.minv[3 * i + 2];
+  for (int i = 0; i < 3; ++i) o.bc[i] = fmaf(r.minv[3 * i], px, r.minv[3 * i + 1] * py) + r.minv[3 * i + 2];
   edge_nearest(px, py, r.x[0], r.y[0], r.x[1] - r.x[0], r.y[1] - r.y[0], r.nx[0], r.ny[0], r.ilen[0], o.t[0], o.d2[0]);
   edge_nearest(px, py, r.x[1], r.y[1], r.x[2] - r.x[1], r.y[2] - r.y[1], r.nx[1], r.ny[1], r.ilen[1], o.t[1], o.d2[1]);
   edge_nearest(px, py, r.x[2], r.y[2], r.x[0] - r.x[2], r.y[0] - r.y[2], r.nx[2], r.ny[2], r.ilen[2], o.t[2], o.d2[2]);
@@ -205,16 +217,16 @@ __device__ __forceinline__ bool eval_pair(const SoftRec &r, const CornerRec *__r
   const float is1 = 1.0f / fmaxf(o.s1, kNormEps);  // F.normalize(p=1), rasterize.py:359-365
 #pragma unroll
   for (int k = 0; k < 3; ++k) o.sb[k] = o.q[k] * is1;
-  const float zz = o.sb[0] * r.zn[0] + o.sb[1] * r.zn[1] + o.sb[2] * r.zn[2];
-  o.z = 0.5f - zz / 2.0f;  // rasterize.py:368-370
+  const float zz = fmaf(o.sb[0], r.zn[0], o.sb[1] * r.zn[1]) + o.sb[2] * r.zn[2];
+  o.z = fmaf(zz, -0.5f, 0.5f);  // 0.5 - zz / 2 (halving is exact), rasterize.py:368-370
   if (o.z < 0.0f || o.z > 1.0f) return false;
 #pragma unroll
   for (int c = 0; c < 3; ++c) {  // rasterize.py:194-196; corner record rows: normal, position, diffuse
-    o.nraw[c] = o.sb[0] * cr.c[0][c] + o.sb[1] * cr.c[1][c] + o.sb[2] * cr.c[2][c];
-    o.pos[c] = o.sb[0] * cr.c[0][3 + c] + o.sb[1] * cr.c[1][3 + c] + o.sb[2] * cr.c[2][3 + c];
-    o.kd[c] = o.sb[0] * cr.c[0][6 + c] + o.sb[1] * cr.c[1][6 + c] + o.sb[2] * cr.c[2][6 + c];
+    o.nraw[c] = fmaf(o.sb[2], cr.c[2][c], fmaf(o.sb[1], cr.c[1][c], o.sb[0] * cr.c[0][c]));
+    o.pos[c] = fmaf(o.sb[2], cr.c[2][3 + c], fmaf(o.sb[1], cr.c[1][3 + c], o.sb[0] * cr.c[0][3 + c]));
+    o.kd[c] = fmaf(o.sb[2], cr.c[2][6 + c], fmaf(o.sb[1], cr.c[1][6 + c], o.sb[0] * cr.c[0][6 + c]));
   }
-  o.nn = sqrtf(o.nraw[0] * o.nraw[0] + o.nraw[1] * o.nraw[1] + o.nraw[2] * o.nraw[2]);
+  o.nn = sqrtf(fmaf(o.nraw[2], o.nraw[2], fmaf(o.nraw[1], o.nraw[1], o.nraw[0] * o.nraw[0])));
   const float inn = 1.0f / fmaxf(o.nn, kNormEps);
 #pragma unroll
   for (int c = 0; c < 3; ++c) o.N[c] = o.nraw[c] * inn;
@@ -223,9 +235,9 @@ __device__ __forceinline__ bool eval_pair(const SoftRec &r, const CornerRec *__r
   for (int l = 0; l < ML; ++l) {  // rasterize.py:197-206 (unrolled: static register indices)
     if (ML > 1 && l >= ls.L) break;
     const float vx = ls.pos[l][0] - o.pos[0], vy = ls.pos[l][1] - o.pos[1], vz = ls.pos[l][2] - o.pos[2];
-    const float ivn = 1.0f / fmaxf(sqrtf(vx * vx + vy * vy + vz * vz), kNormEps);
-    const float ndl = fminf(fmaxf((vx * o.N[0] + vy * o.N[1] + vz * o.N[2]) * ivn, 0.0f), 1.0f);
-    o.lum += ndl * ls.inten[l];
+    const float ivn = 1.0f / fmaxf(sqrtf(fmaf(vz, vz, fmaf(vy, vy, vx * vx))), kNormEps);
+    const float ndl = fminf(fmaxf(fmaf(vz, o.N[2], fmaf(vy, o.N[1], vx * o.N[0])) * ivn, 0.0f), 1.0f);
+    o.lum = fmaf(ndl, ls.inten[l], o.lum);
   }
 #pragma unroll
   for (int c = 0; c < 3; ++c) o.c[c] = o.kd[c] * o.lum;

@@ -252,6 +252,32 @@ def test_soft_oracle_single_triangle_known_answers():
     np.testing.assert_allclose(np.diag(np.fliplr(g["image_a"][..., 3])), 0.5, atol=1e-6)
 
 
+def test_soft_oracle_float32_is_unchanged_by_following_the_dtype():
+    """oracle/soft.py follows the dtype of its inputs (the float64 truth of tests/soft_truth.py) and reports its
+    decisions through trace=.  Its float32 evaluation of the single-triangle scene reproduced the stored images
+    bit for bit before that change, and must still: the stored values, not a second copy of the code, are the
+    'before'.  A float64 call answers in float64, within float32 rounding of the same picture, and a trace
+    changes nothing that is computed."""
+    from oracle import soft
+    g = golden_npz("soft_single_triangle_10x10.npz")
+    args = [_t(g[k]) for k in ("clip", "triangles", "world", "normals", "diffuse", "light_positions", "light_intensities")]
+    for tag in ("a", "b"):
+        sig, gam, blur = [float(v) for v in g["params_" + tag]]
+        img = soft.rasterize_batch(*args, 10, 10, sig, gam, blur)
+        assert img.dtype == torch.float32 and torch.equal(img, _t(g["image_" + tag])), tag
+        trace = {}
+        assert torch.equal(soft.rasterize_batch(*args, 10, 10, sig, gam, blur, trace=trace), img)
+        for key, shape in (("cand", (100, 1)), ("inside", (100, 1)), ("keep", (100, 1)), ("edge", (100, 1)),
+                           ("bc", (100, 1, 3)), ("edge_dist", (100, 1, 3)), ("sq_dist", (100, 1)), ("t_raw", (100, 1)),
+                           ("t_raw_edges", (100, 1, 3)), ("z", (100, 1)), ("ndl_raw", (100, 1, 1)), ("lo", (1, 2)),
+                           ("hi", (1, 2)), ("area", (1,)), ("valid", (1,)), ("p2", (100, 2))):
+            assert tuple(trace[key].shape) == shape and not trace[key].requires_grad, key
+        wide = [a.double() if a.is_floating_point() else a for a in args]
+        img64 = soft.rasterize_batch(*wide, 10, 10, sig, gam, blur)
+        assert img64.dtype == torch.float64
+        np.testing.assert_allclose(img64.numpy(), g["image_" + tag], atol=1e-6, rtol=0)
+
+
 def test_soft_oracle_point_to_segment_nearest():
     """The vectors the reference's own test holds for point_to_segment_nearest (test_rasterize.py:9-44:
     the first three cases, with the answers written there) and 256 more through the reference function
