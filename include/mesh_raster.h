@@ -805,6 +805,41 @@ int mr_nearest_backward(const float *x, const float *y, const int32_t *x_lengths
                         const float *grad_points, const float *grad_images, float x_weight, float y_weight, float *dx,
                         float *dy, void *stream);
 
+/* ---- K nearest neighbours between point clouds (no reference counterpart) ----
+ * Per image b, for every query x_i with i < x_lengths[b], the K targets y_j with j < y_lengths[b] that have the K
+ * SMALLEST 64-bit keys  (bits of (x_i - y_j).(x_i - y_j) << 32) | j,  in ascending key order (INTEGRATION.md,
+ * "K nearest neighbours"); the distance in the difference form, as mr_nearest_forward.  Equal float32 distances go
+ * to the lowest index, and a NaN distance (a bit pattern above +inf's) sorts after every number, whatever the launch
+ * shape, the split count or K: the first K' columns of a K-neighbour call are the K'-neighbour call, bit for bit.
+ *   x [B,N,3], y [B,M,3] f32;  x_lengths, y_lengths [B] i32 (device) or NULL, clamped to [0, N] / [0, M] by the kernels
+ *   sqdist [B,N,K] f32 out, idx [B,N,K] i32 out.  A slot whose distance is NaN reports sqdist +inf; its idx, like
+ *   every idx of a valid slot, lies in [0, y_lengths[b]).  A slot k >= y_lengths[b] and every slot of a padded query
+ *   (i >= x_lengths[b]) get sqdist 0, idx -1.  Padded coordinates influence nothing.
+ * mr_knn_plan: the launch shape, a pure host function: every lane keeps `queries_per_lane` sorted lists of
+ * `list_capacity` keys (K rounded up to 4, 8, 16 or 32) in registers; the targets are cut into `splits` runs of whole
+ * `target_tile`s as for mr_nearest_forward.  With splits > 1 every run writes its K keys per query into the workspace
+ * (B * splits * N * K * 8 bytes, rounded up to 256; 0 without a split) and a second pass keeps the K smallest:
+ * order-independent, no atomics.
+ *
+ * mr_knn_backward: the gradient of  sum_ik g_ik sqdist_ik  (grad [B,N,K] f32) from the saved sqdist and idx:
+ *   dx_i = sum_k 2 g_ik (x_i - y_idx_ik),   dy_j = -sum_{(i,k): idx_ik = j} 2 g_ik (x_i - y_j)
+ *   order [B,N*K], offsets [B,M+1] i32: the inverted index of idx flattened to [B,N*K] (entry e belongs to query
+ *         e / K), as for mr_nearest_backward: a stable sort with -1 last; needed when dy is asked for
+ *   dx [B,N,3], dy [B,M,3] f32 out or NULL (not computed); each is written completely, padded rows 0
+ * A slot with idx -1, an idx outside the other cloud, or a sqdist that is not finite contributes nothing.  Eight
+ * lanes per destination row and a fixed butterfly: no atomics, no zero-fills, bit-reproducible in either
+ * deterministic mode.  All entry points only enqueue on `stream`: capturable in a HIP graph.
+ * 1 <= K <= 32; B, N, M as for mr_nearest_forward, and N * K < 2^31, B * N * K < 2^36; anything else is MR_EINVAL
+ * (queries return 0) before a device is touched. */
+int mr_knn_plan(int B, int N, int M, int K, int *splits, int *queries_per_lane, int *list_capacity, int *target_tile,
+                int *workgroup_size);
+size_t mr_knn_workspace_bytes(int B, int N, int M, int K);
+int mr_knn_forward(const float *x, const float *y, const int32_t *x_lengths, const int32_t *y_lengths, int B, int N,
+                   int M, int K, float *sqdist, int32_t *idx, void *workspace, size_t workspace_bytes, void *stream);
+int mr_knn_backward(const float *x, const float *y, const int32_t *x_lengths, const int32_t *y_lengths, int B, int N,
+                    int M, int K, const float *sqdist, const int32_t *idx, const int32_t *order, const int32_t *offsets,
+                    const float *grad, float *dx, float *dy, void *stream);
+
 /* ---- point to nearest triangle: the point-to-mesh distance (no reference counterpart) ----
  * Per image b, for every query p_i with i < lengths[b], over the T triangles of one shared topology
  * ("Point-cloud losses"):

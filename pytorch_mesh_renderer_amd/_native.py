@@ -378,6 +378,18 @@ def lib():
         except AttributeError as e:   # the mesh-to-point entry points came without an ABI version bump
             raise NativeLibraryError("%s lacks the nearest-point-of-triangle entry points (%s): rebuild it (make -C "
                                      "pytorch_mesh_renderer_amd/csrc)" % (LIB_PATH, e))
+        try:
+            L.mr_knn_plan.argtypes = [ci] * 4 + [vp] * 5
+            L.mr_knn_plan.restype = ci
+            L.mr_knn_workspace_bytes.argtypes = [ci] * 4
+            L.mr_knn_workspace_bytes.restype = sz
+            L.mr_knn_forward.argtypes = [vp] * 4 + [ci] * 4 + [vp, vp, vp, sz, vp]
+            L.mr_knn_forward.restype = ci
+            L.mr_knn_backward.argtypes = [vp] * 4 + [ci] * 4 + [vp] * 8
+            L.mr_knn_backward.restype = ci
+        except AttributeError as e:   # the K-nearest-neighbour entry points came without an ABI version bump
+            raise NativeLibraryError("%s lacks the K-nearest-neighbour entry points (%s): rebuild it (make -C "
+                                     "pytorch_mesh_renderer_amd/csrc)" % (LIB_PATH, e))
         _lib = L
     return _lib
 
@@ -1145,6 +1157,81 @@ def nearest_backward(x, y, x_lengths, y_lengths, idx_xy=None, index_xy=None, idx
         rc = L.mr_nearest_backward(*[_ptr(t) for t in held[:4]], B, N, M, *[_ptr(t) for t in held[4:]],
                                    float(x_weight), float(y_weight), _ptr(dx), _ptr(dy), _stream(dev))
     _check(rc, "mr_nearest_backward")
+    return dx, dy
+
+
+KNN_MAX_K = 32
+
+
+def knn_plan(B, N, M, K):
+    """The launch shape mr_knn_forward takes for B images of N queries against M targets and K neighbours, a pure
+    host function: {"splits", "queries_per_lane", "list_capacity", "target_tile", "workgroup_size"}
+    (include/mesh_raster.h)."""
+    out = (ctypes.c_int * 5)()
+    rc = lib().mr_knn_plan(int(B), int(N), int(M), int(K),
+                           *[ctypes.c_void_p(ctypes.addressof(out) + 4 * k) for k in range(5)])
+    if rc != MR_OK:
+        raise ValueError("knn_plan takes 1..65535 images of 1..2^28 points and 1..%d neighbours with N * K < 2^31, got "
+                         "(%r, %r, %r, %r)" % (KNN_MAX_K, B, N, M, K))
+    return dict(zip(("splits", "queries_per_lane", "list_capacity", "target_tile", "workgroup_size"), list(out)))
+
+
+def _chk_knn(x, y, x_lengths, y_lengths, K):
+    B, N, M = _chk_clouds(x, y, x_lengths, y_lengths)
+    if not isinstance(K, int) or isinstance(K, bool) or not 1 <= K <= KNN_MAX_K:
+        raise ValueError("K must be an int in [1, %d], got %r" % (KNN_MAX_K, K))
+    if N * K >= 1 << 31 or B * N * K >= 1 << 36:
+        raise ValueError("the K-nearest-neighbour kernels take N * K < 2^31 and B * N * K < 2^36, got %s with K = %d"
+                         % (list(x.shape), K))
+    return B, N, M
+
+
+def knn_forward(x, y, K, x_lengths=None, y_lengths=None):
+    """x [B,N,3], y [B,M,3] f32, lengths [B] i32 or None (device) -> (sqdist [B,N,K] f32, idx [B,N,K] i32):
+    mr_knn_forward."""
+    B, N, M = _chk_knn(x, y, x_lengths, y_lengths, K)
+    dev = _require_device(x, y, *[t for t in (x_lengths, y_lengths) if t is not None])
+    L = lib()
+    x, y = x.contiguous(), y.contiguous()
+    x_lengths = x_lengths.contiguous() if x_lengths is not None else None
+    y_lengths = y_lengths.contiguous() if y_lengths is not None else None
+    sqdist = torch.empty(B, N, K, dtype=_F32, device=dev)
+    idx = torch.empty(B, N, K, dtype=_I32, device=dev)
+    with torch.cuda.device(dev):
+        ws, have = _workspace(dev, L.mr_knn_workspace_bytes(B, N, M, K))
+        rc = L.mr_knn_forward(_ptr(x), _ptr(y), _ptr(x_lengths), _ptr(y_lengths), B, N, M, K, _ptr(sqdist), _ptr(idx),
+                              _ptr(ws), have, _stream(dev))
+    _check(rc, "mr_knn_forward")
+    return sqdist, idx
+
+
+def knn_backward(x, y, x_lengths, y_lengths, sqdist, idx, grad, index=None, want_dx=True, want_dy=True):
+    """mr_knn_backward -> (dx [B,N,3] or None, dy [B,M,3] or None).  sqdist, idx [B,N,K]: what knn_forward returned;
+    grad [B,N,K] f32; index: nearest_inverted_index(idx.reshape(B, N * K), M), needed for dy."""
+    _chk("idx", idx, _I32, None, None, None)
+    K = int(idx.shape[2])
+    B, N, M = _chk_knn(x, y, x_lengths, y_lengths, K)
+    _chk("idx", idx, _I32, B, N, K)
+    _chk("sqdist", sqdist, _F32, B, N, K)
+    _chk("upstream gradient", grad, _F32, B, N, K)
+    tensors = [x, y, sqdist, idx, grad] + [t for t in (x_lengths, y_lengths) if t is not None]
+    if index is not None:
+        _chk("order", index[0], _I32, B, N * K)
+        _chk("offsets", index[1], _I32, B, M + 1)
+        tensors += list(index)
+    elif want_dy:
+        raise ValueError("the targets' gradient needs the inverted index of idx")
+    dev = _require_device(*tensors)
+    L = lib()
+    c = lambda t: t.contiguous() if t is not None else None
+    order, offsets = index if index is not None else (None, None)
+    dx = torch.empty(B, N, 3, dtype=_F32, device=dev) if want_dx else None
+    dy = torch.empty(B, M, 3, dtype=_F32, device=dev) if want_dy else None
+    held = [c(t) for t in (x, y, x_lengths, y_lengths, sqdist, idx, order, offsets, grad)]
+    with torch.cuda.device(dev):
+        rc = L.mr_knn_backward(*[_ptr(t) for t in held[:4]], B, N, M, K, *[_ptr(t) for t in held[4:]], _ptr(dx),
+                               _ptr(dy), _stream(dev))
+    _check(rc, "mr_knn_backward")
     return dx, dy
 
 

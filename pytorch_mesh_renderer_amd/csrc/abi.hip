@@ -920,6 +920,44 @@ int mr_nearest_backward(const float *x, const float *y, const int32_t *x_lengths
                                      (hipStream_t)stream);
 }
 
+inline bool bad_knn_dims(int B, int N, int M, int K) {
+  return bad_nearest_dims(B, N, M) || K < 1 || K > mr::knn_max_k() || (size_t)N * K > (size_t)INT_MAX ||
+         (size_t)B * N * K >= ((size_t)1 << 36);
+}
+
+int mr_knn_plan(int B, int N, int M, int K, int *splits, int *queries_per_lane, int *list_capacity, int *target_tile,
+                int *workgroup_size) {
+  if (bad_knn_dims(B, N, M, K) || !splits || !queries_per_lane || !list_capacity || !target_tile || !workgroup_size)
+    return MR_EINVAL;
+  mr::knn_plan(B, N, M, K, splits, queries_per_lane, list_capacity, target_tile, workgroup_size);
+  return MR_OK;
+}
+
+size_t mr_knn_workspace_bytes(int B, int N, int M, int K) {
+  if (bad_knn_dims(B, N, M, K)) return 0;
+  return mr::knn_ws(B, N, M, K);
+}
+
+int mr_knn_forward(const float *x, const float *y, const int32_t *x_lengths, const int32_t *y_lengths, int B, int N,
+                   int M, int K, float *sqdist, int32_t *idx, void *workspace, size_t workspace_bytes, void *stream) {
+  if (bad_knn_dims(B, N, M, K)) return MR_EINVAL;
+  if (!x || !y || !sqdist || !idx) return MR_EINVAL;
+  const int rc = check_ws(workspace, workspace_bytes, mr::knn_ws(B, N, M, K));
+  if (rc != MR_OK) return rc;
+  return mr::launch_knn_forward(x, y, x_lengths, y_lengths, B, N, M, K, sqdist, idx, workspace, (hipStream_t)stream);
+}
+
+int mr_knn_backward(const float *x, const float *y, const int32_t *x_lengths, const int32_t *y_lengths, int B, int N,
+                    int M, int K, const float *sqdist, const int32_t *idx, const int32_t *order, const int32_t *offsets,
+                    const float *grad, float *dx, float *dy, void *stream) {
+  if (bad_knn_dims(B, N, M, K)) return MR_EINVAL;
+  if (!x || !y || !sqdist || !idx || !grad) return MR_EINVAL;
+  if ((order == nullptr) != (offsets == nullptr)) return MR_EINVAL;
+  if (dy && !order) return MR_EINVAL;   // the targets' gradient is a gather over the inverted index
+  return mr::launch_knn_backward(x, y, x_lengths, y_lengths, B, N, M, K, sqdist, idx, order, offsets, grad, dx, dy,
+                                 (hipStream_t)stream);
+}
+
 inline bool bad_nearest_triangle_dims(int B, int N, int V, int T) {
   return bad_nearest_dims(B, N, T) || V < 1 || V > (1 << 28) || (size_t)B * V >= ((size_t)1 << 36);
 }

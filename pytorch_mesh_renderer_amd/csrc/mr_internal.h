@@ -271,6 +271,16 @@ int launch_nearest_backward(const float *x, const float *y, const int32_t *x_len
                             const int32_t *idx_yx, const int32_t *order_yx, const int32_t *offsets_yx,
                             const float *grad_points, const float *grad_images, float x_weight, float y_weight,
                             float *dx, float *dy, hipStream_t s);
+// K nearest neighbours between point clouds, mr_knn_* (nearest.hip)
+int knn_max_k();
+void knn_plan(int B, int N, int M, int K, int *splits, int *queries_per_lane, int *list_capacity, int *target_tile,
+              int *workgroup);
+size_t knn_ws(int B, int N, int M, int K);
+int launch_knn_forward(const float *x, const float *y, const int32_t *x_lengths, const int32_t *y_lengths, int B, int N,
+                       int M, int K, float *sqdist, int32_t *idx, void *ws, hipStream_t s);
+int launch_knn_backward(const float *x, const float *y, const int32_t *x_lengths, const int32_t *y_lengths, int B, int N,
+                        int M, int K, const float *sqdist, const int32_t *idx, const int32_t *order,
+                        const int32_t *offsets, const float *grad, float *dx, float *dy, hipStream_t s);
 // point to nearest triangle, mr_nearest_triangle_* (nearest.hip)
 void nearest_triangle_plan(int B, int N, int T, int *splits, int *queries_per_lane, int *triangle_tile, int *workgroup);
 size_t nearest_triangle_ws(int B, int N, int T);

@@ -1,7 +1,8 @@
 // Brute-force nearest neighbour between two point clouds on gfx950, the hot path of the Chamfer distance
 // (mr_nearest_forward / _backward; semantics: INTEGRATION.md, "Point-cloud losses"), and further down the same search
 // from points to the triangles of a mesh (mr_nearest_triangle_forward / _backward: "point to triangle") and, last,
-// from the triangles to the points (mr_nearest_point_of_triangle_forward / _backward: "triangle to point").
+// from the triangles to the points (mr_nearest_point_of_triangle_forward / _backward: "triangle to point"), and the
+// K-neighbour form of the point search (mr_knn_forward / _backward: "K nearest neighbours").
 //
 // Per image b, for every query x_i (i < x_lengths[b]) over the targets y_j (j < y_lengths[b]):
 //   sqdist_i = min_j (x_i - y_j).(x_i - y_j),   idx_i = the lowest j that attains it
@@ -828,6 +829,231 @@ __global__ __launch_bounds__(kThreads) void k_tp_backward_points(
   if (have && sub == 0) dpoints[(size_t)b * N + p] = V3{dx, dy, dz};
 }
 
+// ---- K nearest neighbours ---------------------------------------------------------------------------------------
+// mr_knn_forward / _backward: per image, for every query x_i the K targets y_j with the K smallest 64-bit keys
+// (bits of (x_i - y_j).(x_i - y_j) << 32) | j, in ascending key order ("K nearest neighbours").  The
+// search is k_nearest's -- targets broadcast from LDS, the difference form, splits of whole tiles (plan_of) -- with
+// the running (best, index) pair replaced by a sorted LIST of C keys per query that lives in registers: C, the
+// capacity, is K rounded up to 4, 8, 16 or 32 and a template parameter, every subscript of the list is a constant
+// after unrolling (a runtime subscript would send it to scratch), and the list is truncated to K on output.  A new
+// key is compared with the list's worst first; only a winner replaces it and walks the compare-exchange chain down
+// (C - 1 steps of one 64-bit compare and four selects).  Any lane of a wavefront that inserts makes all 64 walk it.
+// Equal distances order by index and a NaN's bit pattern is above +inf's, so a NaN sorts after every number and the
+// result depends on neither the capacity nor the launch shape; the distance is spelled with explicit fused
+// multiply-adds so that the scalar and the packed instantiations round alike (as tri_candidates).  A split writes
+// its K keys per query to the workspace, k_knn_merge keeps the K smallest of splits x K with the same list.
+//
+// Backward of sum_ik g_ik |x_i - y_idx_ik|^2: k_nearest_backward's eight lanes per destination row and butterfly;
+// a query's row walks its own K slots, a target's row the inverted index of the flattened [N K] indices (entry e
+// belongs to query e / K).  Slots with idx -1 or a distance that is not finite contribute nothing.
+constexpr int kKnnMaxK = 32;
+constexpr int knn_wide_queries(int C) { return C <= 4 ? 4 : (C <= 8 ? 2 : 1); }   // 2 C VGPRs of keys a query
+inline int knn_capacity_of(int K) { return K <= 4 ? 4 : (K <= 8 ? 8 : (K <= 16 ? 16 : 32)); }
+inline Plan knn_plan_of(int B, int N, int M, int K) {
+  return plan_of(B, N, M, kTile, knn_wide_queries(knn_capacity_of(K)));
+}
+inline size_t knn_keys_bytes(const Plan &p, int B, int N, int K) {
+  return p.splits > 1 ? align_up((size_t)B * p.splits * N * K * sizeof(unsigned long long), 256) : 0;
+}
+
+__device__ __forceinline__ unsigned long long key_of(float d, int j) {
+  return ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)j;
+}
+
+// The C smallest keys offered so far, ascending; kNoKey where fewer were offered.
+template <int C>
+struct KeyList {
+  unsigned long long k[C];
+  __device__ __forceinline__ void clear() {
+#pragma unroll
+    for (int s = 0; s < C; ++s) k[s] = kNoKey;
+  }
+  __device__ __forceinline__ void offer(unsigned long long key) {
+    if (key < k[C - 1]) {   // most keys stop here
+      k[C - 1] = key;
+#pragma unroll
+      for (int s = C - 1; s > 0; --s) {
+        const unsigned long long below = k[s - 1], above = k[s];
+        const bool swap = above < below;
+        k[s - 1] = swap ? above : below;
+        k[s] = swap ? below : above;
+      }
+    }
+  }
+};
+
+template <typename F>
+__device__ __forceinline__ F knn_distance(F px, F py, F pz, float ax, float ay, float az) {
+#pragma clang fp contract(off)   // the fused multiply-adds are spelled: every instantiation rounds alike
+  const F dx = px - (F)ax, dy = py - (F)ay, dz = pz - (F)az;
+  return fma_of(dz, dz, fma_of(dy, dy, dx * dx));
+}
+
+// Slot k of a query's final list -> sqdist, idx: (0, -1) for a padded row and beyond the image's valid targets
+__device__ __forceinline__ void knn_write(unsigned long long key, bool row_valid, int k, int mv,
+                                          float *__restrict__ sqdist, int32_t *__restrict__ idx, size_t at) {
+  const bool valid = row_valid && k < mv && key != kNoKey;
+  const float d = __uint_as_float((unsigned)(key >> 32));
+  sqdist[at] = valid ? (d != d ? INFINITY : d) : 0.0f;
+  idx[at] = valid ? min((int)(unsigned)(key & 0xffffffffull), mv - 1) : -1;
+}
+
+// grid (query blocks, splits, B).  keys != null (splits > 1): K keys per (image, split, query), [B, splits, K, N];
+// keys == null: the final sqdist / idx [B, N, K].
+template <int C, int Q>
+__global__ __launch_bounds__(kThreads) void k_knn(const float *__restrict__ x, const float *__restrict__ y,
+                                                  const int32_t *__restrict__ x_lengths,
+                                                  const int32_t *__restrict__ y_lengths, int N, int M, int K, int chunk,
+                                                  float *__restrict__ sqdist, int32_t *__restrict__ idx,
+                                                  unsigned long long *__restrict__ keys) {
+  __shared__ __attribute__((aligned(16))) float sx[kTile];
+  __shared__ __attribute__((aligned(16))) float sy[kTile];
+  __shared__ __attribute__((aligned(16))) float sz[kTile];
+  const int b = (int)blockIdx.z, split = (int)blockIdx.y;
+  const int nv = valid_count(x_lengths, b, N), mv = valid_count(y_lengths, b, M);
+  const float *xb = x + (size_t)b * N * 3;
+  const float *yb = y + (size_t)b * M * 3;
+  const int j0 = min(split * chunk, mv), j1 = min(j0 + chunk, mv);   // this split's targets, maybe none
+  const int i0 = (int)blockIdx.x * (kThreads * Q) + (int)threadIdx.x;
+
+  float px[Q], py[Q], pz[Q];
+  KeyList<C> list[Q];
+#pragma unroll
+  for (int q = 0; q < Q; ++q) {
+    const int i = i0 + q * kThreads;
+    const bool have = i < nv;
+    px[q] = have ? xb[3 * (size_t)i] : 0.0f;
+    py[q] = have ? xb[3 * (size_t)i + 1] : 0.0f;
+    pz[q] = have ? xb[3 * (size_t)i + 2] : 0.0f;
+    list[q].clear();
+  }
+
+  for (int t0 = j0; t0 < j1; t0 += kTile) {   // j0, j1: the same on every thread
+    const int count = min(kTile, j1 - t0);
+    const int padded = (count + 3) & ~3;   // staged as zeros beyond count and never offered
+    __syncthreads();
+    for (int f = (int)threadIdx.x; f < 3 * padded; f += kThreads) {
+      const int j = f / 3, c = f - 3 * j;
+      const float v = j < count ? yb[3 * (size_t)t0 + f] : 0.0f;
+      float *plane = c == 0 ? sx : (c == 1 ? sy : sz);
+      plane[j] = v;
+    }
+    __syncthreads();
+    for (int j = 0; j < padded; j += 4) {
+      const float4 tx = *reinterpret_cast<const float4 *>(&sx[j]);
+      const float4 ty = *reinterpret_cast<const float4 *>(&sy[j]);
+      const float4 tz = *reinterpret_cast<const float4 *>(&sz[j]);
+      const float ax[4] = {tx.x, tx.y, tx.z, tx.w};
+      const float ay[4] = {ty.x, ty.y, ty.z, ty.w};
+      const float az[4] = {tz.x, tz.y, tz.z, tz.w};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (j + k < count) {   // (the same on every thread)
+          const int t = t0 + j + k;
+          if constexpr (Q % 2 == 0) {
+#pragma unroll
+            for (int q = 0; q < Q; q += 2) {
+              const F2 d = knn_distance(F2{px[q], px[q + 1]}, F2{py[q], py[q + 1]}, F2{pz[q], pz[q + 1]}, ax[k],
+                                        ay[k], az[k]);
+              list[q].offer(key_of(d.x, t));
+              list[q + 1].offer(key_of(d.y, t));
+            }
+          } else {
+#pragma unroll
+            for (int q = 0; q < Q; ++q)
+              list[q].offer(key_of(knn_distance(px[q], py[q], pz[q], ax[k], ay[k], az[k]), t));
+          }
+        }
+      }
+    }
+  }
+
+#pragma unroll
+  for (int q = 0; q < Q; ++q) {
+    const int i = i0 + q * kThreads;
+    if (i >= N) continue;
+#pragma unroll
+    for (int k = 0; k < C; ++k) {
+      if (k < K) {
+        if (keys)
+          keys[(((size_t)b * gridDim.y + split) * K + k) * N + i] = i < nv ? list[q].k[k] : kNoKey;
+        else
+          knn_write(list[q].k[k], i < nv, k, mv, sqdist, idx, ((size_t)b * N + i) * K + k);
+      }
+    }
+  }
+}
+
+// The K smallest of a query's splits x K keys -> sqdist, idx.  grid (ceil(N / kThreads), B)
+template <int C>
+__global__ __launch_bounds__(kThreads) void k_knn_merge(const unsigned long long *__restrict__ keys, int splits,
+                                                        const int32_t *__restrict__ x_lengths,
+                                                        const int32_t *__restrict__ y_lengths, int N, int M, int K,
+                                                        float *__restrict__ sqdist, int32_t *__restrict__ idx) {
+  const int b = (int)blockIdx.y;
+  const int i = (int)blockIdx.x * kThreads + (int)threadIdx.x;
+  if (i >= N) return;
+  const int nv = valid_count(x_lengths, b, N), mv = valid_count(y_lengths, b, M);
+  KeyList<C> list;
+  list.clear();
+  if (i < nv)
+    for (int s = 0; s < splits; ++s)
+      for (int k = 0; k < K; ++k) list.offer(keys[(((size_t)b * splits + s) * K + k) * N + i]);
+#pragma unroll
+  for (int k = 0; k < C; ++k) {
+    if (k < K) knn_write(list.k[k], i < nv, k, mv, sqdist, idx, ((size_t)b * N + i) * K + k);
+  }
+}
+
+// dp[b, p] for one cloud p (Np points) against the other cloud o (No points), over the saved sqdist / idx / grad
+// [B, N, K] of N queries: the sum of 2 g_e (p - o_e) over the row's entries e.  kTargets false: p is the queries'
+// cloud (Np == N), row p's entries are its own K slots and o_e = y[idx_e].  kTargets true: p is the targets' cloud,
+// the entries are order[offsets[p] .. offsets[p + 1]) of the inverted index (order [B, N K], offsets [B, Np + 1]) and
+// o_e = x[e / K].  Eight lanes per row.  grid (ceil(Np / kPointsPerBlock), B)
+template <bool kTargets>
+__global__ __launch_bounds__(kThreads) void k_knn_backward(
+    const V3 *__restrict__ p_points, const V3 *__restrict__ o_points, const int32_t *__restrict__ p_lengths,
+    const int32_t *__restrict__ o_lengths, int Np, int No, int N, int K, const float *__restrict__ sqdist,
+    const int32_t *__restrict__ idx, const int32_t *__restrict__ order, const int32_t *__restrict__ offsets,
+    const float *__restrict__ grad, V3 *__restrict__ dp) {
+  const int b = (int)blockIdx.y;
+  const int p = (int)blockIdx.x * kPointsPerBlock + (int)threadIdx.x / kLanesPerPoint;
+  const int sub = (int)threadIdx.x % kLanesPerPoint;
+  const bool have = p < Np;   // (whole groups of eight: the butterfly below stays inside one)
+  const int pv = valid_count(p_lengths, b, Np), ov = valid_count(o_lengths, b, No);
+  const int entries = N * K;   // (below 2^31: mr_knn_*'s limits)
+  const size_t base = (size_t)b * entries;
+  const V3 *ob = o_points + (size_t)b * No;
+  float dx = 0.0f, dy = 0.0f, dz = 0.0f;
+  if (have && p < pv) {
+    const V3 me = p_points[(size_t)b * Np + p];
+    int e0 = p * K, e1 = e0 + K;
+    if constexpr (kTargets) {
+      const int32_t *off = offsets + (size_t)b * (Np + 1);
+      e0 = max(off[p], 0), e1 = min(off[p + 1], entries);
+    }
+    for (int k = e0 + sub; k < e1; k += kLanesPerPoint) {
+      int e = k, other;
+      if constexpr (kTargets) {
+        e = order[base + k];
+        if ((unsigned)e >= (unsigned)entries || idx[base + e] != p) continue;
+        other = e / K;
+      } else {
+        other = idx[base + e];
+      }
+      if ((unsigned)other >= (unsigned)ov) continue;
+      if (!(sqdist[base + e] < INFINITY)) continue;   // a distance that is +inf or NaN has no gradient
+      const float g2 = 2.0f * grad[base + e];
+      const V3 o = ob[other];
+      dx += g2 * (me.x - o.x);
+      dy += g2 * (me.y - o.y);
+      dz += g2 * (me.z - o.z);
+    }
+  }
+  dx = group_sum(dx), dy = group_sum(dy), dz = group_sum(dz);
+  if (have && sub == 0) dp[(size_t)b * Np + p] = V3{dx, dy, dz};
+}
+
 inline Plan tri_plan_of(int B, int N, int T) { return plan_of(B, N, T, kTriTile, kTriWideQueries); }
 inline size_t tri_records_bytes(int B, int T) { return align_up((size_t)B * T * kRecWords * sizeof(float4), 256); }
 // triangle to point: the T triangles are the queries, one a lane, and the N points the targets that are split
@@ -1055,6 +1281,75 @@ int launch_nearest_point_of_triangle_backward(const float *points, const float *
     hipLaunchKernelGGL(k_nt_backward_vertices<true>, grid, dim3(kThreads), 0, s, (const V3 *)points,
                        (const V3 *)vertices, triangles, lengths, N, V, T, index, (const V3 *)bary, corner_order,
                        corner_offsets, grad_triangles, grad_images, usable, (V3 *)dvertices);
+    return check_launch();
+  }
+  return MR_OK;
+}
+
+int knn_max_k() { return kKnnMaxK; }
+
+void knn_plan(int B, int N, int M, int K, int *splits, int *queries_per_lane, int *list_capacity, int *target_tile,
+              int *workgroup) {
+  const Plan p = knn_plan_of(B, N, M, K);
+  *splits = p.splits;
+  *queries_per_lane = p.queries_per_lane;
+  *list_capacity = knn_capacity_of(K);
+  *target_tile = kTile;
+  *workgroup = kThreads;
+}
+
+// the splits' keys; nothing without a split
+size_t knn_ws(int B, int N, int M, int K) { return knn_keys_bytes(knn_plan_of(B, N, M, K), B, N, K); }
+
+namespace {
+
+template <int C>
+int launch_knn_of(const Plan &p, const float *x, const float *y, const int32_t *x_lengths, const int32_t *y_lengths,
+                  int B, int N, int M, int K, float *sqdist, int32_t *idx, void *ws, hipStream_t s) {
+  constexpr int kWide = knn_wide_queries(C);
+  unsigned long long *keys = p.splits > 1 ? (unsigned long long *)ws : nullptr;
+  const dim3 grid((unsigned)p.query_blocks, (unsigned)p.splits, (unsigned)B);
+  if (kWide > 1 && p.queries_per_lane == kWide)
+    hipLaunchKernelGGL((k_knn<C, kWide>), grid, dim3(kThreads), 0, s, x, y, x_lengths, y_lengths, N, M, K, p.chunk,
+                       sqdist, idx, keys);
+  else
+    hipLaunchKernelGGL((k_knn<C, 1>), grid, dim3(kThreads), 0, s, x, y, x_lengths, y_lengths, N, M, K, p.chunk, sqdist,
+                       idx, keys);
+  int rc = check_launch();
+  if (rc != MR_OK || !keys) return rc;
+  hipLaunchKernelGGL(k_knn_merge<C>, dim3(merge_blocks_of(N), (unsigned)B), dim3(kThreads), 0, s,
+                     (const unsigned long long *)keys, p.splits, x_lengths, y_lengths, N, M, K, sqdist, idx);
+  return check_launch();
+}
+
+}  // namespace
+
+int launch_knn_forward(const float *x, const float *y, const int32_t *x_lengths, const int32_t *y_lengths, int B, int N,
+                       int M, int K, float *sqdist, int32_t *idx, void *ws, hipStream_t s) {
+  const Plan p = knn_plan_of(B, N, M, K);
+  switch (knn_capacity_of(K)) {
+    case 4: return launch_knn_of<4>(p, x, y, x_lengths, y_lengths, B, N, M, K, sqdist, idx, ws, s);
+    case 8: return launch_knn_of<8>(p, x, y, x_lengths, y_lengths, B, N, M, K, sqdist, idx, ws, s);
+    case 16: return launch_knn_of<16>(p, x, y, x_lengths, y_lengths, B, N, M, K, sqdist, idx, ws, s);
+    default: return launch_knn_of<32>(p, x, y, x_lengths, y_lengths, B, N, M, K, sqdist, idx, ws, s);
+  }
+}
+
+int launch_knn_backward(const float *x, const float *y, const int32_t *x_lengths, const int32_t *y_lengths, int B, int N,
+                        int M, int K, const float *sqdist, const int32_t *idx, const int32_t *order,
+                        const int32_t *offsets, const float *grad, float *dx, float *dy, hipStream_t s) {
+  if (dx) {
+    const dim3 grid((unsigned)((N + kPointsPerBlock - 1) / kPointsPerBlock), (unsigned)B);
+    hipLaunchKernelGGL(k_knn_backward<false>, grid, dim3(kThreads), 0, s, (const V3 *)x, (const V3 *)y, x_lengths,
+                       y_lengths, N, M, N, K, sqdist, idx, (const int32_t *)nullptr, (const int32_t *)nullptr, grad,
+                       (V3 *)dx);
+    const int rc = check_launch();
+    if (rc != MR_OK) return rc;
+  }
+  if (dy) {
+    const dim3 grid((unsigned)((M + kPointsPerBlock - 1) / kPointsPerBlock), (unsigned)B);
+    hipLaunchKernelGGL(k_knn_backward<true>, grid, dim3(kThreads), 0, s, (const V3 *)y, (const V3 *)x, y_lengths,
+                       x_lengths, M, N, N, K, sqdist, idx, order, offsets, grad, (V3 *)dy);
     return check_launch();
   }
   return MR_OK;

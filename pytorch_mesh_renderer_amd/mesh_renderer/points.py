@@ -10,6 +10,9 @@ Distances are always computed as (x - y).(x - y), never as |x|^2 + |y|^2 - 2 x.y
 point_mesh_distance measure to the mesh's surface itself -- the nearest closed triangle -- with kernels of the same
 file and the same split between the HIP and the torch path; triangle_nearest_points and mesh_point_distance are the
 other direction, every triangle against its nearest point, and point_mesh_face_distance is the sum of the two means.
+knn_points is the K-neighbour form of nearest_points (a sorted list of K keys per query in registers, same file, same
+split between the two paths), knn_gather reads values at its indices, and estimate_point_normals is its first
+consumer: the normals of a scan from the covariance of every point's neighbourhood.
 """
 import torch
 from torch.autograd.function import once_differentiable
@@ -195,6 +198,186 @@ def chamfer_distance(x, y, x_lengths=None, y_lengths=None, x_weight=1.0, y_weigh
         if y_weight != 0.0:
             total = total + y_weight * _mean_torch(_nearest_torch(y, x, y_lengths, x_lengths)[0], y_lengths, x_lengths)
     return total[0] if single else total
+
+
+# ---- K nearest neighbours ---------------------------------------------------------------------------------------------
+
+class _Knn(torch.autograd.Function):
+    """knn_points on the HIP path: (sqdist [B,N,K], idx [B,N,K]) of x -> y."""
+
+    @staticmethod
+    def forward(ctx, x, y, x_lengths, y_lengths, K):
+        xd, yd = x.detach().contiguous(), y.detach().contiguous()
+        sqdist, idx = _native.knn_forward(xd, yd, K, x_lengths, y_lengths)
+        ctx.save_for_backward(xd, yd, x_lengths, y_lengths, sqdist, idx)
+        ctx.mark_non_differentiable(idx)
+        return sqdist, idx
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad, _unused=None):
+        x, y, x_lengths, y_lengths, sqdist, idx = ctx.saved_tensors
+        want_dx, want_dy = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        none = (None,) * 3
+        if not (want_dx or want_dy):
+            return (None, None) + none
+        # the targets' gradient is a gather over the inverted index of the [B, N K] entries; nothing else needs it
+        index = _inverted_index(idx.reshape(idx.shape[0], -1), y.shape[1]) if want_dy else None
+        dx, dy = _native.knn_backward(x, y, x_lengths, y_lengths, sqdist, idx, grad.contiguous(), index,
+                                      want_dx=want_dx, want_dy=want_dy)
+        return (dx, dy) + none
+
+
+def _knn_torch(x, y, K, x_lengths, y_lengths):
+    """knn_points as a torch expression on the device and in the dtype of x [B,N,3] / y [B,M,3]: the neighbours are
+    selected chunk by chunk of queries without a graph, by a stable sort of the distances (so equal distances go to
+    the lowest index, NaN after every number, targets beyond y_lengths last); the distances to them are then an
+    ordinary differentiable gather."""
+    B, N, _ = x.shape
+    M = y.shape[1]
+    dev = x.device
+    n_valid = x_lengths.long() if x_lengths is not None else torch.full((B,), N, dtype=torch.int64, device=dev)
+    m_valid = y_lengths.long() if y_lengths is not None else torch.full((B,), M, dtype=torch.int64, device=dev)
+    outside = torch.arange(M, device=dev)[None, None, :] >= m_valid[:, None, None]          # [B,1,M]
+    rows = max(1, _CHUNK_BYTES // max(1, B * M * 3 * x.element_size()))
+    kept = min(K, M)
+    found = []
+    with torch.no_grad():
+        for start in range(0, N, rows):
+            diff = x[:, start:start + rows, None, :] - y[:, None, :, :]
+            d = (diff * diff).sum(-1).masked_fill(outside, float("nan"))
+            found.append(torch.sort(d, dim=2, stable=True).indices[..., :kept])
+        idx = torch.cat(found, dim=1)
+        if kept < K:
+            idx = torch.cat([idx, idx.new_zeros(B, N, K - kept)], dim=2)
+        slot = torch.arange(K, device=dev)[None, None, :]
+        valid = (torch.arange(N, device=dev)[None, :, None] < n_valid[:, None, None]) & (slot < m_valid[:, None, None])
+        idx = torch.where(valid, idx, torch.full_like(idx, -1))
+    diff = x[:, :, None, :] - knn_gather(y, idx)
+    with torch.no_grad():
+        finite = torch.isfinite((diff * diff).sum(-1))
+    diff = torch.where((valid & finite)[..., None], diff, torch.zeros_like(diff))   # value 0, gradient 0
+    sqdist = (diff * diff).sum(-1)
+    sqdist = torch.where(valid & ~finite, torch.full_like(sqdist, float("inf")), sqdist)
+    return sqdist, idx.to(torch.int32)
+
+
+def knn_gather(values, idx):
+    """values [B,M,C], idx [B,N,K] integer (or [M,C], [N,K]) -> [B,N,K,C]: values[b, idx[b,i,k]], zeros where idx is
+    -1.  A torch gather: differentiable in values, and a slot with idx -1 passes no gradient."""
+    if not torch.is_tensor(values) or not torch.is_tensor(idx):
+        raise TypeError("values and idx must be tensors")
+    if idx.is_floating_point() or idx.is_complex() or idx.dtype == torch.bool:
+        raise RuntimeError("idx must hold integer indices")
+    single = values.dim() == 2
+    v, i = (values.unsqueeze(0), idx.unsqueeze(0)) if single else (values, idx)
+    if v.dim() != 3 or i.dim() != 3 or v.shape[0] != i.shape[0]:
+        raise ValueError("values must have shape [B, M, C] and idx [B, N, K] (or [M, C] and [N, K]), got %s and %s"
+                         % (list(values.shape), list(idx.shape)))
+    if v.device != i.device:
+        raise RuntimeError("values and idx must be on the same device")
+    B, N, K = i.shape
+    C = v.shape[2]
+    safe = i.long().clamp(0, v.shape[1] - 1)
+    out = torch.gather(v, 1, safe.reshape(B, N * K, 1).expand(-1, -1, C)).reshape(B, N, K, C)
+    out = torch.where((i >= 0)[..., None], out, torch.zeros_like(out))
+    return out[0] if single else out
+
+
+def knn_points(x, y, K, x_lengths=None, y_lengths=None, return_nn=False):
+    """x [B,N,3], y [B,M,3] (or [N,3], [M,3]: one image, results without the batch axis), K a Python int in [1, 32]
+    -> (sqdist [B,N,K], idx [B,N,K] int32[, nn [B,N,K,3] with return_nn]): for every x[b,i] its K nearest y[b,j]
+    with j < y_lengths[b], nearest first, ordered by (squared Euclidean distance, j): equally distant targets come
+    lowest index first.  sqdist (and nn = knn_gather(y, idx)) are differentiable in x and y; idx is not.
+
+    x_lengths, y_lengths as in nearest_points.  A slot k >= y_lengths[b] (fewer than K targets) and every slot of a
+    padded query row get sqdist 0, idx -1 and no gradient; padded coordinates influence nothing.  A distance that is
+    NaN sorts after every number; its slot reports sqdist +inf with an idx in [0, y_lengths[b]), and a slot whose
+    distance is not finite passes no gradient.  On a HIP device with float32 clouds the search is csrc/nearest.hip's
+    (a sorted list of K keys per query in registers; no N x M tensor); otherwise a chunked torch expression."""
+    x, y, x_lengths, y_lengths, single = _arguments(x, y, x_lengths, y_lengths)
+    if not isinstance(K, int) or isinstance(K, bool) or not 1 <= K <= _native.KNN_MAX_K:
+        raise ValueError("K must be an int in [1, %d], got %r" % (_native.KNN_MAX_K, K))
+    if _on_hip_path(x):
+        sqdist, idx = _Knn.apply(x, y, x_lengths, y_lengths, K)
+    else:
+        sqdist, idx = _knn_torch(x, y, K, x_lengths, y_lengths)
+    out = (sqdist, idx, knn_gather(y, idx)) if return_nn else (sqdist, idx)
+    return tuple(t[0] for t in out) if single else out
+
+
+def _smallest_eigenvectors(c):
+    """c [...,3,3] symmetric float64 -> (unit eigenvectors of the smallest eigenvalue [...,3], eigenvalues [...,3]
+    ascending), in closed form with elementwise ops: the trigonometric eigenvalues, then the largest of the three cross
+    products of the rows of c - lambda_0 I.  The zero vector where lambda_1 - lambda_0 <= 1e-12 lambda_2."""
+    c00, c11, c22 = c[..., 0, 0], c[..., 1, 1], c[..., 2, 2]
+    c01, c02, c12 = c[..., 0, 1], c[..., 0, 2], c[..., 1, 2]
+    q = (c00 + c11 + c22) / 3.0
+    off = c01 * c01 + c02 * c02 + c12 * c12
+    p = (((c00 - q) ** 2 + (c11 - q) ** 2 + (c22 - q) ** 2 + 2.0 * off) / 6.0).sqrt()
+    safe = p.clamp(min=1e-300)
+    b00, b11, b22, b01, b02, b12 = ((c00 - q) / safe, (c11 - q) / safe, (c22 - q) / safe, c01 / safe, c02 / safe,
+                                    c12 / safe)
+    det = b00 * (b11 * b22 - b12 * b12) - b01 * (b01 * b22 - b12 * b02) + b02 * (b01 * b12 - b11 * b02)
+    phi = torch.acos((det / 2.0).clamp(-1.0, 1.0)) / 3.0
+    high = q + 2.0 * p * torch.cos(phi)
+    low = q + 2.0 * p * torch.cos(phi + 2.0943951023931953)   # + 2 pi / 3
+    mid = 3.0 * q - high - low
+    rows = c - low[..., None, None] * torch.eye(3, dtype=c.dtype, device=c.device)
+    crosses = torch.stack([torch.cross(rows[..., 0, :], rows[..., 1, :], dim=-1),
+                           torch.cross(rows[..., 0, :], rows[..., 2, :], dim=-1),
+                           torch.cross(rows[..., 1, :], rows[..., 2, :], dim=-1)], dim=-2)      # [...,3,3]
+    norms = crosses.norm(dim=-1)
+    which = norms.argmax(dim=-1)
+    vector = torch.gather(crosses, -2, which[..., None, None].expand(*which.shape, 1, 3))[..., 0, :]
+    length = torch.gather(norms, -1, which[..., None])
+    usable = (mid - low > 1e-12 * high) & (length[..., 0] > 0)
+    vector = torch.where(usable[..., None], vector / length.clamp(min=1e-300), torch.zeros_like(vector))
+    return vector, torch.stack([low, mid, high], dim=-1)
+
+
+def estimate_point_normals(points, K=16, lengths=None, orient_to=None):
+    """points [B,N,3] (or [N,3]) -> unit normals [B,N,3] in the points' dtype: for every point the direction of least
+    variance of its K nearest points of the same cloud, the point itself included (knn_points(points, points, K,
+    lengths, lengths)): the covariance about the neighbourhood's mean in float64 and the eigenvector of its smallest
+    eigenvalue in closed form (elementwise torch ops on the points' device, no solver).
+
+    A neighbourhood with fewer than 3 valid points, a collinear one (lambda_1 - lambda_0 <= 1e-12 lambda_2) and a
+    padded row get the zero vector.  Sign: with orient_to ([3] or [B,3], a sensor position) so that
+    n . (orient_to - p) >= 0; otherwise the component of largest magnitude is positive (the lowest axis of equal
+    magnitudes).  NOT differentiable: the scan is data, and the result carries no graph."""
+    _cloud("points", points)
+    single = points.dim() == 2
+    p = points.detach().unsqueeze(0) if single else points.detach()
+    B = p.shape[0]
+    if single and torch.is_tensor(lengths) and lengths.dim() == 0:
+        lengths = lengths.reshape(1)
+    if orient_to is not None:
+        if not torch.is_tensor(orient_to) or not orient_to.is_floating_point():
+            raise TypeError("orient_to must be a floating-point tensor")
+        if orient_to.shape not in ((3,), (B, 3)):
+            raise ValueError("orient_to must have shape [3] or [%d, 3], got %s" % (B, list(orient_to.shape)))
+        if orient_to.device != p.device:
+            raise RuntimeError("orient_to must be on the points' device")
+    with torch.no_grad():
+        sqdist, idx = knn_points(p, p, K, lengths, lengths)
+        valid = (idx >= 0) & torch.isfinite(sqdist)                               # [B,N,K]
+        p64 = p.double()
+        count = valid.sum(-1, keepdim=True).clamp(min=1).double()                 # [B,N,1]
+        near = knn_gather(p64, idx)                                               # [B,N,K,3], zeros where invalid
+        mean = near.sum(2) / count
+        centred = torch.where(valid[..., None], near - mean[:, :, None, :], torch.zeros_like(near))
+        covariance = (centred[..., :, None] * centred[..., None, :]).sum(2) / count[..., None]
+        normals, _ = _smallest_eigenvectors(covariance)
+        normals = torch.where((valid.sum(-1) >= 3)[..., None], normals, torch.zeros_like(normals))
+        if orient_to is not None:
+            towards = orient_to.detach().double().reshape(-1, 1, 3) - p64
+            flip = (normals * towards).sum(-1, keepdim=True) < 0
+        else:
+            lead = torch.gather(normals, -1, normals.abs().argmax(dim=-1, keepdim=True))
+            flip = lead < 0
+        normals = torch.where(flip, -normals, normals).to(points.dtype)
+    return normals[0] if single else normals
 
 
 def _mesh(vertices, triangles):
