@@ -938,8 +938,10 @@ int mr_nearest_point_of_triangle_backward(const float *points, const float *vert
  *   eye, center, up [B,3] f32; fov_y (degrees), near_clip, far_clip [B] f32; aspect = width / height
  *   transforms [B,4,4] f32 out, row-major
  *   degenerate  1 int32 out (device): bit 0 = some |center - eye| <= 1e-6, bit 1 = some
- *               |forward x up| <= 1e-6 -- the two conditions the reference asserts on
- *               (camera_utils.py:68-69, 74-76); the caller decides when to read it back
+ *               |forward x up| <= 1e-6 on a camera that has a forward vector (bit 0 not raised by
+ *               it) -- the two conditions the reference asserts on, in its order
+ *               (camera_utils.py:68-69, 74-76); a NaN input raises both; the caller decides when
+ *               to read it back
  *   dtransforms [B,4,4] f32; deye, dcenter, dup [B,3] f32 out */
 int mr_camera_transforms(const float *eye, const float *center, const float *up, const float *fov_y,
                          const float *near_clip, const float *far_clip, float aspect, int B, float *transforms,

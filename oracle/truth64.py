@@ -225,7 +225,9 @@ def phong(ids, bary, tris, normals, positions, diffuse, light_positions, light_i
     render.py:384-386).  Arrays in, dict of float64 arrays out:
       d_normals, d_positions (the attribute path only), d_diffuse [B,V,3], d_specular, d_shininess,
       d_light_positions, d_light_intensities [B,L,3], d_ambient [B,3], d_camera [B,3], image [B,H,W,4],
-      dbary [B,H,W,3], gabs [B,H,W] (for raster_pullback), noise_normals / _positions / _diffuse [B,V,3]."""
+      dbary [B,H,W,3], gabs [B,H,W] (for raster_pullback), noise_normals / _positions / _diffuse [B,V,3],
+      noise_camera [B,3] (with a specular term: the sum over the pixels of |d loss / d unit view vector| / distance,
+      times the conditioning of the difference the view vector is made of)."""
     B, H, W = ids.shape
     leaves, groups, per_vertex = _leaves(normals, positions, diffuse, light_positions, light_intensities, ambient,
                                          specular, shininess, camera_position)
@@ -263,7 +265,11 @@ def phong(ids, bary, tris, normals, positions, diffuse, light_positions, light_i
         dp = dp + (kept["to_light"].grad.abs().sum(3) / (kept["to_light_len"] + tiny) * cond).sum(1)
     if "to_cam" in kept and kept["to_cam"].grad is not None:
         cond = torch.clamp((pmag[:, 0] + leaves["camera"].detach().abs().sum(1).unsqueeze(1)) / (kept["to_cam_len"] + tiny), min=1.0)
-        dp = dp + kept["to_cam"].grad.abs().sum(2) / (kept["to_cam_len"] + tiny) * cond
+        per_pixel = kept["to_cam"].grad.abs().sum(2) / (kept["to_cam_len"] + tiny) * cond
+        dp = dp + per_pixel
+        # the camera position meets the same unit vector with the opposite sign: d_camera is the sum over the pixels of
+        # what the positions get through it, and its noise scale the sum of those magnitudes
+        out["noise_camera"] = per_pixel.sum(1, keepdim=True).expand(B, 3).numpy().copy()
     dat[..., 3:6] = torch.maximum(dat[..., 3:6], dp.reshape(B, H, W, 1))
     if "pow_cond" in kept:   # the gradients that exist only through the power: specular colours, per-vertex exponents
         dat[..., 9:] = dat[..., 9:] * kept["pow_cond"].reshape(B, H, W, 1)

@@ -200,7 +200,10 @@ __global__ __launch_bounds__(kThreads) void k_camera_transforms(
   const V3 e = eye[b];
   const Camera c = camera_frame(e, center[b], up[b], fov_y[b], near_clip[b], far_clip[b], aspect);
   // the reference's two assertions (camera_utils.py:68-69, 74-76): bit 0 eye ~ center, bit 1 up ~ gaze
-  const int flags = (!(c.f_len > kCameraDegenerate) ? 1 : 0) | (!(c.s_len > kCameraDegenerate) ? 2 : 0);
+  // Bit 1 is judged only where there is a gaze to judge it by: with eye == center the forward vector is 0 / 0 and
+  // |f x up| a NaN whatever the up vector (the reference stops at its first assertion).  A NaN input raises both.
+  const bool no_gaze = c.f_len <= kCameraDegenerate;
+  const int flags = (!(c.f_len > kCameraDegenerate) ? 1 : 0) | (!(c.s_len > kCameraDegenerate) && !no_gaze ? 2 : 0);
   if (flags) atomicOr(degenerate, flags);
   // view = R T: rows (s, -s.e), (u, -u.e), (-f, f.e), (0 0 0 1); clip = P view
   const float v0[4] = {c.s.x, c.s.y, c.s.z, -dot(c.s, e)};

@@ -1,5 +1,7 @@
 """Shared by the CPU and GPU tests: the float64 truth (oracle/truth64.py) of a reference golden scene or of a
 random soup, from the G-buffer a forward pass produced."""
+import functools
+
 import numpy as np
 import torch
 
@@ -44,3 +46,108 @@ def golden_scene_truth(g, ids, bary, clip, transforms):
                        g["light_positions"], g["light_intensities"], g["ambient"] if "ambient" in g.files else None,
                        golden_upstream(g), specular=spec, shininess=shin,
                        camera_position=g["eye"] if spec is not None else None)
+
+
+# ---- camera gradients: d clip -> d transforms -> d (eye, center, up) -----------------------------------------------------
+
+def camera_chain_truth(cameras, aspect, positions, d_clip, noise_clip, d_camera=None, noise_camera=None):
+    """The clip-space gradient pulled back to the cameras, in float64, with its noise scale.
+
+    cameras: dict of float32 tensors eye, center, up [B,3], fov, near, far [B] (tests/camera_reference.py);
+    positions [B,V,3]: the world-space vertices; d_clip, noise_clip [B,V,4]: truth64.raster_pullback's.
+
+        d_xf[b,r,k]   = sum_v d_clip[b,v,r] (v, 1)[k]          noise_xf = sum_v noise_clip[b,v,r] |(v, 1)[k]|
+        d_(eye, center, up) = J^T d_xf                          noise    = |J|^T noise_xf + 8 |f32 - f64|
+
+    J being camera_reference.jacobian and the last term the float32 restatement of the camera backward on d_xf against its
+    float64 -- the camera chain's own conditioning, from the reference alone.  d_camera / noise_camera [B,3] (the specular
+    term's view vector, truth64.phong) are added to the eye's.  -> {"eye" | "center" | "up": (gradient, noise)} [B,3]."""
+    import camera_reference as cr
+    pos = np.asarray(positions, dtype=np.float64)
+    B = pos.shape[0]
+    v1 = np.concatenate([pos, np.ones(pos.shape[:2] + (1,))], axis=2)
+    d_xf = np.einsum("bvr,bvk->brk", np.asarray(d_clip, dtype=np.float64), v1)
+    noise_xf = np.einsum("bvr,bvk->brk", np.asarray(noise_clip, dtype=np.float64), np.abs(v1))
+    args = [cameras[k] for k in ("eye", "center", "up", "fov", "near", "far")]
+    J = cr.jacobian(*args, aspect).numpy()                                   # [B,16,9]
+    grad = np.einsum("bik,bi->bk", J, d_xf.reshape(B, 16))
+    noise = np.einsum("bik,bi->bk", np.abs(J), noise_xf.reshape(B, 16))
+    w = torch.tensor(d_xf)
+    _, g64 = cr.transforms(*args, aspect, torch.float64, w)
+    _, g32 = cr.transforms(*args, aspect, torch.float32, w)
+    out = {}
+    for i, k in enumerate(cr.INPUTS):
+        out[k] = (grad[:, 3 * i:3 * i + 3].copy(),
+                  noise[:, 3 * i:3 * i + 3] + 8.0 * (g32[k].double() - g64[k]).abs().numpy())
+    if d_camera is not None:
+        out["eye"] = (out["eye"][0] + np.asarray(d_camera, dtype=np.float64), out["eye"][1] + np.asarray(noise_camera, dtype=np.float64))
+    return out
+
+
+CAMERA_SCENES = ("cube", "sphere", "soup")
+COVERAGE = (0.05, 0.95)       # the share of covered pixels a camera of these scenes must keep, per image
+_LIGHTS = [[2.0, 3.0, 4.0], [-3.0, 1.0, 2.5], [0.5, -2.5, 3.0]]
+
+
+def coverage(ids, bary):
+    """[B]: the share of covered pixels per image."""
+    return truth64.covered_mask(np.asarray(ids), np.asarray(bary)).reshape(len(ids), -1).mean(1)
+
+
+@functools.lru_cache(maxsize=None)
+def camera_scene(name):
+    """A small two-image scene with a different plain-family camera (tests/camera_reference.py) per image -> dict of host
+    float32 tensors: vertices, normals, diffuse, specular [2,V,3], triangles [T,3] i32, light_positions, light_intensities
+    [2,3,3] (callers cut the lights they want), ambient [2,3], W, H, cameras (eye, center, up [2,3], fov, near, far [2]).
+    The cameras are the first of the family, in its order, that keep between 15 and 85 % of the oracle rasterizer's pixels
+    covered with every vertex in front of the eye: the margin to COVERAGE is for the device's own rounding."""
+    import camera_reference as cr
+    import oracle
+    from pytorch_mesh_renderer_amd.common import camera_utils, shapes, synthetic
+    g = torch.Generator().manual_seed(sum(map(ord, name)))
+    if name == "cube":
+        W, H = 64, 48
+        v, tri, n = shapes.cube(2.0)
+        tri = torch.flip(tri, [1]).contiguous()              # clockwise faces the viewer, as the examples do
+        vertices = torch.stack([v, v + 0.1 * torch.randn(v.shape, generator=g)])
+        normals = torch.stack([n, n + 0.2 * torch.randn(n.shape, generator=g)])
+    elif name == "sphere":
+        W, H = 64, 48
+        job = synthetic.sphere_job(2, W, H, 8)
+        tri = job["triangles"]
+        vertices = job["vertices"] + 0.02 * torch.randn(job["vertices"].shape, generator=g)
+        normals = job["normals"] + 0.1 * torch.randn(job["normals"].shape, generator=g)
+    elif name == "soup":
+        import backward_fuzz
+        rng = np.random.default_rng(77)
+        for trial in range(64):                              # the first two-image soup of the stream
+            B, V, T, W, H, pos, _, tris = backward_fuzz.soup(rng, trial, True)
+            if B == 2:
+                break
+        assert B == 2
+        vertices, tri = torch.tensor(pos), torch.tensor(tris)
+        normals = torch.randn(2, V, 3, generator=g)
+    else:
+        raise KeyError(name)
+    V = vertices.shape[1]
+    scene = {"vertices": vertices.float().contiguous(), "normals": normals.float().contiguous(), "triangles": tri.to(torch.int32),
+             "diffuse": 0.1 + 0.9 * torch.rand(2, V, 3, generator=g), "specular": 0.1 + 0.9 * torch.rand(2, V, 3, generator=g),
+             "light_positions": torch.tensor(_LIGHTS)[None] + 0.3 * torch.randn(2, 3, 3, generator=g),
+             "light_intensities": 0.3 + 0.7 * torch.rand(2, 3, 3, generator=g), "ambient": 0.3 * torch.rand(2, 3, generator=g),
+             "W": W, "H": H}
+    family = cr.family("plain", cr.SIZE)
+    order = ("eye", "center", "up", "fov", "near", "far")
+    chosen, i = [], 0
+    while len(chosen) < 2:
+        assert i < cr.SIZE, "no plain camera sees enough of %s" % name
+        one = {k: family[k][i:i + 1] for k in order}
+        xf, _ = cr.transforms(*[one[k] for k in order], W / H, torch.float32)
+        b = len(chosen)
+        clip = camera_utils.transform_homogeneous(xf, scene["vertices"][b:b + 1]).contiguous()
+        ids, bary, _ = oracle.forward(clip.numpy(), scene["triangles"].numpy(), W, H)
+        if 0.15 <= float(coverage(ids, bary)[0]) <= 0.85 and float(clip[..., 3].min()) > float(one["near"]):
+            chosen.append(i)
+        i += 1
+    scene["cameras"] = {k: family[k][chosen].contiguous() for k in order}
+    scene["camera_ids"] = tuple(chosen)
+    return scene
