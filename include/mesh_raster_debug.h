@@ -40,6 +40,17 @@ int mr_debug_set_raster_repeat(int n);
  * make sure the specialised kernel they pin to the reference's gradients is the one that ran.  Static storage. */
 const char *mr_debug_last_accumulate_kernel(void);
 
+/* Strip height of the lane-accumulating pixel pass (k_accumulate_lanes: rows a wavefront walks down its 64-pixel-wide
+ * strip) for the calling thread's next launches.  0 = automatic (default): the functor's own height, 16 for the
+ * rasterizer backward, halved down to 4 while the launch would leave wavefront slots of the chip empty -- so every
+ * small image runs 4-row strips.  4 / 8 / 16 force that height, so that the tests can run all three on small images;
+ * anything else: MR_EINVAL.  The strip count behind the workspace of the per-strip sums follows the setting.  Results
+ * differ only in the order of the float sums. */
+int mr_debug_set_lanes_rows(int rows);
+
+/* Strip height the most recent k_accumulate_lanes launch of any thread of this process used (0 before the first). */
+int mr_debug_last_lanes_rows(void);
+
 /* Stage-timing probes of k_raster.  Only a library built with -DMR_PROBES (make probes ->
  * libmesh_raster_hip_probes.so) contains the probe instantiations; the production library
  * returns MR_EINVAL for every value but 0, its kernel has no probe code at all.

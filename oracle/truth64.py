@@ -33,13 +33,14 @@ def covered_mask(ids, bary):
     return (np.asarray(ids) != 0) | (np.asarray(bary, dtype=np.float64).sum(-1) >= 0.9)
 
 
-def raster_pullback(clip, tris, ids, bary, dbary, gabs=None):
+def raster_pullback(clip, tris, ids, bary, dbary, gabs=None, stats=None):
     """-> (dclip [B,V,4] float64, noise [B,V,4] float64).
 
     clip [B,V,4], ids [B,H,W], bary [B,H,W,3]: the forward's inputs / outputs (float32 bits);
     dbary [B,H,W,3] float64: dL / d barycentrics; gabs [B,H,W] (optional): a magnitude for dL/db's
     entries in the noise scale (default: max_i |dbary_i|) -- pass the larger sum of |products| when
-    dbary itself comes out of a cancellation."""
+    dbary itself comes out of a cancellation.  stats (optional dict): receives "max_partial", the largest
+    |b_j * bracket_k| of any one pixel (what the deterministic mode's fixed-point range has to hold)."""
     clip = np.asarray(clip, dtype=np.float64)
     tris = np.asarray(tris).astype(np.int64)
     B, V = clip.shape[:2]
@@ -78,6 +79,10 @@ def raster_pullback(clip, tris, ids, bary, dbary, gabs=None):
         S = minv.sum(1)                                             # [n,k]
         bracket = -(g[:, :, None] * minv).sum(1) + S * (g * bb).sum(1)[:, None]   # [n,k]
         nb = 2.0 * ga[:, None] * minv_abs.sum(1)                    # [n,k]
+        if stats is not None:
+            with np.errstate(invalid="ignore"):
+                largest = float(np.abs(bb[:, :, None] * bracket[:, None, :]).max())
+            stats["max_partial"] = max(stats.get("max_partial", 0.0), largest if np.isfinite(largest) else np.inf)
         for j in range(3):
             for k in range(3):
                 np.add.at(dclip[b, :, comp[k]], tri[:, j], bb[:, j] * bracket[:, k])

@@ -79,6 +79,17 @@ def debug_last_accumulate_kernel():
     return text.split("Fn = mr::")[-1].rstrip("]").replace("(anonymous namespace)::", "") if "Fn = " in text else text
 
 
+def debug_set_lanes_rows(rows):
+    """Tests only (include/mesh_raster_debug.h): strip height of the lane-accumulating pixel pass for THIS thread's next
+    launches -- 0 automatic (default), 4 / 8 / 16 forced."""
+    _check(lib().mr_debug_set_lanes_rows(int(rows)), "mr_debug_set_lanes_rows")
+
+
+def debug_last_lanes_rows():
+    """Tests only: strip height the most recent lane-accumulating launch used (0 before the first)."""
+    return int(lib().mr_debug_last_lanes_rows())
+
+
 def debug_soft_nearest(points, seg_a, seg_b):
     """Tests only (include/mesh_raster_debug.h): the SoftRas kernels' nearest-point-on-a-segment
     evaluation for [n,2] device points / segment ends -> [n,4] = (nearest x, y, t, squared distance)."""
@@ -167,6 +178,10 @@ def lib():
         L.mr_debug_set_raster_repeat.restype = ci
         L.mr_debug_last_accumulate_kernel.argtypes = []
         L.mr_debug_last_accumulate_kernel.restype = ctypes.c_char_p
+        L.mr_debug_set_lanes_rows.argtypes = [ci]
+        L.mr_debug_set_lanes_rows.restype = ci
+        L.mr_debug_last_lanes_rows.argtypes = []
+        L.mr_debug_last_lanes_rows.restype = ci
         L.mr_debug_soft_nearest.argtypes = [vp, vp, vp, ci, vp, vp]
         L.mr_debug_soft_nearest.restype = ci
         L.mr_rasterize_forward_workspace_bytes.argtypes = [ci] * 5

@@ -31,6 +31,8 @@ thread_local KernelTimerSlot g_kernel_timers[MR_TIMER_COUNT];
 extern thread_local int g_deterministic;
 extern thread_local int g_shade_backward_kernel;
 const char *volatile g_last_accumulate_kernel = "";
+thread_local int g_lanes_rows = 0;
+volatile int g_last_lanes_rows = 0;
 }
 
 extern "C" {
@@ -79,6 +81,14 @@ int mr_debug_set_raster_repeat(int n) {
 }
 
 const char *mr_debug_last_accumulate_kernel(void) { return mr::g_last_accumulate_kernel; }
+
+int mr_debug_set_lanes_rows(int rows) {
+  if (rows != 0 && rows != 4 && rows != 8 && rows != 16) return MR_EINVAL;
+  mr::g_lanes_rows = rows;
+  return MR_OK;
+}
+
+int mr_debug_last_lanes_rows(void) { return mr::g_last_lanes_rows; }
 
 int mr_debug_set_raster_probe(int probe) {
 #ifdef MR_PROBES

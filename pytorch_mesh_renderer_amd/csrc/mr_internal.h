@@ -94,6 +94,10 @@ inline hipError_t zero_async(void *ptr, size_t bytes, hipStream_t s) {
 // compiler spells it -- e.g. "... [Fn = mr::ShadeFoldLaneFn<1, true>]".  The parity tests read it to make sure the
 // specialised kernel they mean to pin to the reference is the one that ran.  One relaxed pointer store per launch.
 extern const char *volatile g_last_accumulate_kernel;
+// mr_debug_set_lanes_rows / mr_debug_last_lanes_rows (mesh_raster_debug.h): the calling thread's forced strip height
+// of k_accumulate_lanes (0: automatic, the default) and the height the last such launch of any thread used.
+extern thread_local int g_lanes_rows;
+extern volatile int g_last_lanes_rows;
 
 // mr_time_next_kernel (mesh_raster.h): per-thread, one-shot pairs of HIP events recorded on the
 // launch stream immediately around one named kernel.  A caller arms a pair, the next launch of

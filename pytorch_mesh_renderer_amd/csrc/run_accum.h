@@ -793,9 +793,11 @@ inline int launch_accumulate_rows(const Fn &fn, int B, int T, int W, int H, floa
 // Rows a wavefront of k_accumulate_lanes walks down its 64-pixel-wide strip: Fn::kLaneRowsPerWave
 // (16 at 1024^2 x 32: 8 -> +1 %, 32 -> +7 %), halved while the launch would leave wavefront slots of
 // the chip empty (256^2 x 8 in 16-row strips is 512 wavefronts for 4096 slots: the rasterizer
-// backward took 0.082 ms there against the rows kernel's 0.054).
+// backward took 0.082 ms there against the rows kernel's 0.054).  A test may force 4, 8 or 16 for its thread
+// (mr_debug_set_lanes_rows): every height is then reachable on a small image; the strip count follows.
 template <class Fn>
 inline int lanes_rows_per_wave(int B, int W, int H) {
+  if (g_lanes_rows != 0) return g_lanes_rows;  // forced by a test (mr_debug_set_lanes_rows)
   int rows = Fn::kLaneRowsPerWave;
   const long columns = (long)B * ((W + kWave - 1) / kWave);
   while (rows > 4 && columns * ((H + rows - 1) / rows) < 8192) rows /= 2;
@@ -811,6 +813,7 @@ inline int launch_accumulate_lanes(const Fn &fn, int B, int T, int W, int H, flo
                                    hipStream_t s, const DetBlock *det = nullptr) {
   g_last_accumulate_kernel = __PRETTY_FUNCTION__;
   const int rows = lanes_rows_per_wave<Fn>(B, W, H);
+  g_last_lanes_rows = rows;
   const int regions_x = (W + kWave - 1) / kWave;
   const int regions_y = (H + rows - 1) / rows;
   const int per_image = regions_x * regions_y;

@@ -11,6 +11,7 @@ orders of magnitude more than the bound.
                   dense and sign-coded upstream
   specular_trial  mr_shade_specular_backward: rows kernel, SpecFoldLaneFn lanes / folded, SpecCoupledLaneFn (one pass, L <= 2)
   attr_trial      mr_interpolate_raster_backward (rasterize()): rows kernel, AttrFoldLaneFn
+  raster_trial    mr_rasterize_backward: RasterLanesFn, and RasterGradFn in deterministic mode, under the scene's own bound
 
 Used by tests/test_backward_truth_gpu.py (a fixed-seed slice inside `pytest -m gpu`) and by the stand-alone
 fuzzers tests/fuzz_shade_backward_gpu.py / tests/fuzz_lane_variants_gpu.py (thousands of trials).
@@ -41,12 +42,22 @@ class Report:
 
     def __init__(self, dump_dir=None):
         self.worst, self.failures, self.trials, self.with_gradients = {}, [], 0, 0
+        self.det_skipped = 0   # raster_trial: trials whose deterministic run was left out (beyond the fixed-point headroom)
         self.dump_dir = dump_dir or os.environ.get("MR_FUZZ_DUMP_DIR") or os.path.join(
             os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out", "fuzz_failures")
         self.dumps = []
 
-    def check(self, kernel, name, got, truth, noise, what):
-        e = truth64.excess(got.detach().cpu().numpy(), truth, noise, K_ROUNDING, FLOOR)
+    def check(self, kernel, name, got, truth, noise, what, k_scene=None):
+        """k_scene: the scene's own bound k_scene * (2^-24 noise + 1e-7) (raster_backward_scenes: calibrated by the oracle
+        on the same G-buffer) instead of the general K_ROUNDING one."""
+        if k_scene is None:
+            e = truth64.excess(got.detach().cpu().numpy(), truth, noise, K_ROUNDING, FLOOR)
+        else:
+            g = got.detach().cpu().numpy().astype(np.float64)
+            allowed = k_scene * (truth64.U32 * noise + FLOOR)
+            ok = np.isfinite(truth) & np.isfinite(allowed)
+            err = np.where(np.isfinite(g), np.abs(g - truth), np.inf)
+            e = float((err[ok] / allowed[ok]).max()) if ok.any() else 0.0
         self.worst[kernel] = max(self.worst.get(kernel, 0.0), e)
         if not e <= 1.0:
             self.failures.append("%s: %s of %s is %.1f times the rounding bound (max |truth| %.3e)" % (
@@ -371,6 +382,61 @@ def attr_trial(rng, trial, report, small=False):
             report.check(kernel, "d clip", out[1], d_clip, noise_clip, what)
         raised = False
     finally:
+        ev.close(raised)
+
+
+def raster_trial(rng, trial, report, small=False):
+    """mr_rasterize_backward itself (d barycentrics -> d clip) on the same soups: the float path's lane kernel and the
+    deterministic mode's run kernel, each within the SCENE's bound K_scene (2^-24 noise + 1e-7) of the float64 truth
+    (raster_backward_scenes: K_scene = min(64, max(4, 8 r)), r the oracle's own distance from the truth).  The
+    deterministic kernel is skipped (and counted in report.det_skipped) where a pixel's partial is beyond 2^20 times the
+    largest upstream gradient: there its NaN is the overflow policy (det_fixed.h), not a failure."""
+    import oracle
+    import raster_backward_scenes as rs
+    B, V, T, W, H, pos, xf, tris = soup(rng, trial, small)
+    dbary = (rng.normal(size=(B, H, W, 3)) / (H * W)).astype(np.float32)
+    what = "raster trial %d B=%d V=%d T=%d %dx%d" % (trial, B, V, T, W, H)
+    pos_d, xf_d, tris_d, dbary_d = map(_dev, (pos, xf, tris, dbary))
+    clip = _native.vertex_transform(pos_d, xf_d)
+    ids, bary, _ = _native.rasterize_forward(clip, tris_d, W, H)
+    ids_h, bary_h, clip_h = ids.cpu().numpy(), bary.cpu().numpy(), clip.cpu().numpy()
+    stats = {}
+    d_clip, noise = truth64.raster_pullback(clip_h, tris, ids_h, bary_h, dbary.astype(np.float64), stats=stats)
+    reference = oracle.backward(dbary, clip_h, tris, ids_h, bary_h).astype(np.float64)
+    unit = truth64.U32 * noise + rs.FLOOR
+    ok = np.isfinite(d_clip) & np.isfinite(unit)
+    r = float((np.abs(reference - d_clip)[ok] / unit[ok]).max()) if ok.any() else 0.0
+    k_scene = min(rs.K_MAX, max(rs.K_MIN, rs.MARGIN * r))
+    report.trials += 1
+    report.with_gradients += int(ok.any() and float(np.abs(d_clip[ok]).max()) > 0)
+    report.worst["oracle r"] = max(report.worst.get("oracle r", 0.0), r)
+    ev = Evidence(report, what, dict(upstream=dbary, ids=ids_h, bary=bary_h, clip=clip_h, triangles=tris),
+                  upstream=dbary_d, ids=ids, bary=bary, clip=clip, triangles=tris_d)
+    ev.keep_truth(dict(d_clip=d_clip, noise_clip=noise, oracle=reference))
+    raised = True
+    before = _native.set_deterministic(False)
+    try:
+        lanes = _native.rasterize_backward(dbary_d, clip, tris_d, ids, bary)
+        k_lanes = _native.debug_last_accumulate_kernel().split("<")[0]
+        assert k_lanes == "RasterLanesFn", k_lanes
+        ev.keep(k_lanes, d_clip=lanes)
+        report.check(k_lanes, "d clip", lanes, d_clip, noise, what, k_scene=k_scene)
+        gmax = float(np.abs(dbary).max())
+        if stats.get("max_partial", 0.0) < rs.DET_HEADROOM * gmax and ok.all():
+            _native.set_deterministic(True)
+            fixed = _native.rasterize_backward(dbary_d, clip, tris_d, ids, bary)
+            k_fixed = _native.debug_last_accumulate_kernel().split("<")[0] + "/deterministic"
+            again = _native.rasterize_backward(dbary_d, clip, tris_d, ids, bary)
+            assert k_fixed == "RasterGradFn/deterministic", k_fixed
+            ev.keep(k_fixed, d_clip=fixed, d_clip_again=again)
+            report.check(k_fixed, "d clip", fixed, d_clip, noise, what, k_scene=k_scene)
+            if not torch.equal(fixed.view(torch.int32), again.view(torch.int32)):
+                report.failures.append("%s: two deterministic calls differ" % what)
+        else:
+            report.det_skipped += 1
+        raised = False
+    finally:
+        _native.set_deterministic(before)
         ev.close(raised)
 
 

@@ -1,38 +1,27 @@
-"""One-off fuzz of mr_rasterize_backward (the lane-accumulating kernel with its pipelined row loop) against the
-oracle's sequential accumulation on random triangle soups (not collected by pytest).
+"""Fuzz of mr_rasterize_backward on random triangle soups (GPU; not collected by pytest): the lane-accumulating kernel
+with its pipelined row loop and the deterministic mode's run kernel, EACH against the float64 truth
+(oracle/truth64.py) within the scene's own bound K_scene (2^-24 noise + 1e-7) -- backward_fuzz.raster_trial; K_scene
+is calibrated by the oracle on the same G-buffer, never by a kernel (tests/raster_backward_scenes.py).  A fixed-seed
+slice runs inside `pytest -m gpu` (tests/test_backward_truth_gpu.py).
 
     python tests/fuzz_raster_backward_gpu.py [seed]
 
-Soups in front of the eye, 1..1500 triangles with repeated and degenerate ones, images from 1x1 to 400x300,
-1..3 images per call; the G-buffer is the device's own (bit-identical to the oracle's, tests/fuzz_raster_gpu.py).
-Sliver triangles make single gradients huge, so the error is measured relative to the largest gradient of the
-call: end of round 3, seeds 5 and 11: worst 3.5e-6 over 120 soups."""
-import os, sys
+120 soups of backward_fuzz.soup's full-size recipe (slivers, one-pixel triangles, repeated and degenerate triangles,
+images up to 420x300, 1..3 images per call); the G-buffer is the device's own (bit-identical to the oracle's,
+tests/fuzz_raster_gpu.py)."""
+import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
-import numpy as np, torch
-import oracle
-from test_raster_gpu import hip_forward, hip_backward
-dev = torch.device("cuda:0")
-rng = np.random.default_rng(int(sys.argv[1]) if len(sys.argv) > 1 else 5)
-worst = 0.0
-for trial in range(60):
-    V, T = int(rng.integers(3, 200)), int(rng.integers(1, 1500))
-    W, H = int(rng.integers(1, 400)), int(rng.integers(1, 300))
-    B = int(rng.integers(1, 4))
-    scale = float(rng.choice([0.3, 1.0, 2.0]))
-    clip = (rng.normal(size=(B, V, 4)) * [scale, scale, 1.0, 1.0]).astype(np.float32)
-    clip[..., 3] = np.abs(clip[..., 3]) + 0.2
-    tris = rng.integers(0, V, size=(T, 3)).astype(np.int32)
-    ids, bary, z = hip_forward(clip, tris, W, H, dev)
-    dbary = (rng.normal(size=(B, H, W, 3)) / (H * W)).astype(np.float32)
-    got = hip_backward(dbary, clip, tris, ids, bary, dev)
-    want = oracle.backward(dbary, clip, tris, ids, bary)
-    scale_w = np.abs(want).max() + 1e-30
-    err = np.abs(got - want).max() / scale_w
-    worst = max(worst, err)
-    if err > 2e-3:
-        print("trial", trial, "V,T,W,H,B", V, T, W, H, B, "rel err", err, "max|want|", scale_w)
-print("worst relative-to-max error over 60 soups: %.3e" % worst)
-assert worst < 1e-4, "rasterizer backward disagrees with the oracle"
-print("FUZZ OK")
+import backward_fuzz
+
+TRIALS = 120
+seed = int(sys.argv[1]) if len(sys.argv) > 1 else 5
+t0 = time.time()
+report = backward_fuzz.run(backward_fuzz.raster_trial, TRIALS, seed, progress=20)
+for line in report.failures[:40]:
+    print("MISMATCH", line)
+bad = bool(report.failures) or report.with_gradients < TRIALS // 2 or report.det_skipped > TRIALS // 4
+print("FUZZ", "FAILED" if bad else "OK", "%d soups (%d with gradients, %d without the deterministic run), %d values beyond the bound, "
+      "%.0f s; worst error / bound per kernel: %s" % (TRIALS, report.with_gradients, report.det_skipped, len(report.failures),
+                                                     time.time() - t0, report.summary()))
+sys.exit(1 if bad else 0)

@@ -218,13 +218,15 @@ def test_fuzz_harness_reports_a_changed_input_and_leaves_its_evidence(device, tm
     assert any("`bary` is not what the truth was computed from" in f for f in report2.failures), report2.failures
 
 
-@pytest.mark.parametrize("which,trials", [("shade", 200), ("specular", 200), ("attr", 200)])
+@pytest.mark.parametrize("which,trials", [("shade", 200), ("specular", 200), ("attr", 200), ("raster", 200)])
 def test_backward_kernels_against_float64_on_random_soups(device, which, trials):
     """A fixed-seed slice of the stand-alone fuzzers inside the suite: every pixel-pass variant of the three backward
     entry points on random soups (slivers, one-pixel triangles, crowded and ragged images), each within
-    backward_fuzz.K_ROUNDING * 2^-24 * (sum of |terms|) of the float64 truth.  No retries: a trial beyond the bound
+    backward_fuzz.K_ROUNDING * 2^-24 * (sum of |terms|) of the float64 truth (raster: mr_rasterize_backward's two kernels
+    within the scene's own, tighter K_scene of raster_backward_scenes).  No retries: a trial beyond the bound
     fails the test and leaves its inputs, the truth and every kernel's outputs in an .npz (backward_fuzz.Evidence)."""
-    fn = {"shade": backward_fuzz.shade_trial, "specular": backward_fuzz.specular_trial, "attr": backward_fuzz.attr_trial}[which]
+    fn = {"shade": backward_fuzz.shade_trial, "specular": backward_fuzz.specular_trial, "attr": backward_fuzz.attr_trial,
+          "raster": backward_fuzz.raster_trial}[which]
     report = backward_fuzz.run(fn, trials, seed=505, small=True)
     print("%s: %d trials (%d with gradients); excess over the rounding bound per kernel: %s" % (
         which, report.trials, report.with_gradients, report.summary()))
@@ -232,6 +234,8 @@ def test_backward_kernels_against_float64_on_random_soups(device, which, trials)
     assert report.with_gradients >= trials // 2
     expected = {"shade": ("ShadeGradFn/dense", "ShadeFoldLaneFn/dense", "ShadeFoldLaneFn/signs", "ShadeDiffLaneFn/dense", "ShadeDiffLaneFn/signs"),
                 "specular": ("SpecGradFn", "SpecFoldLaneFn/lanes", "SpecFoldLaneFn/folded", "SpecCoupledLaneFn/folded"),
-                "attr": ("AttrFoldLaneFn",)}[which]
+                "attr": ("AttrFoldLaneFn",), "raster": ("RasterLanesFn", "RasterGradFn/deterministic")}[which]
     for kernel in expected:
         assert kernel in report.worst, (kernel, sorted(report.worst))
+    # raster: the deterministic kernel is left out of a trial beyond its fixed-point headroom -- of a quarter at most
+    assert report.det_skipped <= trials // 4, report.det_skipped
