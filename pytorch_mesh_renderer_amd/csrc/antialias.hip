@@ -4,7 +4,10 @@
 // neighbouring pixels whose ids differ (or exactly one of which is covered) is looked at once; the front pixel
 // f's triangle F is left by the segment f->g through one of its edges at t in [0, 1]; if that edge is a
 // silhouette of the mesh, the colours of the two pixels are blended by how far past (or short of) the segment
-// midpoint the edge lies, and t is differentiated with respect to the edge's clip-space vertices.
+// midpoint the edge lies, and t is differentiated with respect to the edge's clip-space vertices.  The derivative is
+// taken at the crossing point of the DECIDED t, P_c = f + t (g - f) with t clamped and rounded as rule 5 left it: where
+// the clamp acted (a G-buffer that does not belong to clip) that is an end of the segment, and the gradient is rule 8's
+// formula there -- neither the slope of the unclamped quotient nor zero (tests/antialias_reference.py says the same).
 //
 // Layout: one lane per pixel, a workgroup is 64 x 4 pixels (one wavefront per row), so that the left / right
 // neighbours of a lane come from the wavefront's own lines and the up / down ones from the lines of the

@@ -6,42 +6,12 @@ import pytest
 import torch
 
 import antialias_reference as ref
+from antialias_scenes import CUBE_EYES, _cube_clip, _soup
 from pytorch_mesh_renderer_amd import _native, mesh_renderer
 from pytorch_mesh_renderer_amd.common import camera_utils, shapes, synthetic
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda:0")
-
-
-def _cameras(eyes, width, height):
-    B = eyes.shape[0]
-    proj = camera_utils.perspective(torch.full((B,), width / height), torch.full((B,), 40.0),
-                                    torch.full((B,), 0.01), torch.full((B,), 10.0))
-    view = camera_utils.look_at(eyes, torch.zeros(B, 3), torch.tensor([[0.0, 1.0, 0.0]]).repeat(B, 1))
-    return torch.matmul(proj, view)
-
-
-def _cube_clip(eyes, width, height):
-    vertices, triangles, _ = shapes.cube(2.0)
-    triangles = torch.flip(triangles, [1]).contiguous()
-    world = vertices.unsqueeze(0).repeat(eyes.shape[0], 1, 1)
-    return camera_utils.transform_homogeneous(_cameras(eyes, width, height), world).contiguous(), triangles
-
-
-CUBE_EYES = torch.tensor([[2.0, 3.0, 6.0], [-4.0, 1.0, 4.5], [0.3, -2.0, 5.0], [5.0, 0.5, -3.0]])
-
-
-def _soup(seed, B=2, T=60, V=90):
-    g = torch.Generator().manual_seed(seed)
-    xy = torch.rand(B, V, 2, generator=g) * 2.4 - 1.2
-    w = torch.rand(B, V, 1, generator=g) + 0.5
-    w[:, :3] = -0.3                                               # a triangle across the camera plane
-    zz = torch.rand(B, V, 1, generator=g) * 1.6 - 0.8
-    clip = torch.cat([xy * w, zz * w, w], 2).contiguous()
-    tris = torch.randint(0, V, (T, 3), generator=g, dtype=torch.int32)
-    strip = torch.arange(T // 2, dtype=torch.int32)
-    tris[: T // 2] = torch.stack([strip, strip + 1, strip + 2], 1)   # a strip: neighbours share edges
-    return clip, tris
 
 
 def _gbuffer(clip, tris, width, height):
