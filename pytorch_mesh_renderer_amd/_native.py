@@ -1073,14 +1073,22 @@ def mesh_regularizer_backward(dterms, vertices, unit_dirs, topology, terms, targ
     return dvertices
 
 
+def _plan(name, args, fields, takes):
+    """One mr_*_plan call: the native function `name` over the int `args`, its outputs under `fields`; it refuses
+    what the matching forward refuses, `takes` says what that is."""
+    out = (ctypes.c_int * len(fields))()
+    rc = getattr(lib(), "mr_" + name)(*[int(a) for a in args],
+                                      *[ctypes.c_void_p(ctypes.addressof(out) + 4 * k) for k in range(len(fields))])
+    if rc != MR_OK:
+        raise ValueError("%s takes %s, got (%s)" % (name, takes, ", ".join("%r" % (a,) for a in args)))
+    return dict(zip(fields, list(out)))
+
+
 def nearest_plan(B, N, M):
     """The launch shape mr_nearest_forward takes for B images of N queries against M targets, a pure host function:
     {"splits", "queries_per_lane", "target_tile", "workgroup_size"} (include/mesh_raster.h)."""
-    out = (ctypes.c_int * 4)()
-    rc = lib().mr_nearest_plan(int(B), int(N), int(M), *[ctypes.c_void_p(ctypes.addressof(out) + 4 * k) for k in range(4)])
-    if rc != MR_OK:
-        raise ValueError("nearest_plan takes 1..65535 images of 1..2^28 points, got (%r, %r, %r)" % (B, N, M))
-    return dict(zip(("splits", "queries_per_lane", "target_tile", "workgroup_size"), list(out)))
+    return _plan("nearest_plan", (B, N, M), ("splits", "queries_per_lane", "target_tile", "workgroup_size"),
+                 "1..65535 images of 1..2^28 points")
 
 
 def _chk_clouds(x, y, x_lengths, y_lengths):
@@ -1182,13 +1190,9 @@ def knn_plan(B, N, M, K):
     """The launch shape mr_knn_forward takes for B images of N queries against M targets and K neighbours, a pure
     host function: {"splits", "queries_per_lane", "list_capacity", "target_tile", "workgroup_size"}
     (include/mesh_raster.h)."""
-    out = (ctypes.c_int * 5)()
-    rc = lib().mr_knn_plan(int(B), int(N), int(M), int(K),
-                           *[ctypes.c_void_p(ctypes.addressof(out) + 4 * k) for k in range(5)])
-    if rc != MR_OK:
-        raise ValueError("knn_plan takes 1..65535 images of 1..2^28 points and 1..%d neighbours with N * K < 2^31, got "
-                         "(%r, %r, %r, %r)" % (KNN_MAX_K, B, N, M, K))
-    return dict(zip(("splits", "queries_per_lane", "list_capacity", "target_tile", "workgroup_size"), list(out)))
+    return _plan("knn_plan", (B, N, M, K),
+                 ("splits", "queries_per_lane", "list_capacity", "target_tile", "workgroup_size"),
+                 "1..65535 images of 1..2^28 points and 1..%d neighbours with N * K < 2^31" % KNN_MAX_K)
 
 
 def _chk_knn(x, y, x_lengths, y_lengths, K):
@@ -1253,13 +1257,9 @@ def knn_backward(x, y, x_lengths, y_lengths, sqdist, idx, grad, index=None, want
 def nearest_triangle_plan(B, N, T):
     """The launch shape mr_nearest_triangle_forward takes for B images of N queries against T triangles, a pure host
     function: {"splits", "queries_per_lane", "triangle_tile", "workgroup_size"} (include/mesh_raster.h)."""
-    out = (ctypes.c_int * 4)()
-    rc = lib().mr_nearest_triangle_plan(int(B), int(N), int(T),
-                                        *[ctypes.c_void_p(ctypes.addressof(out) + 4 * k) for k in range(4)])
-    if rc != MR_OK:
-        raise ValueError("nearest_triangle_plan takes 1..65535 images of 1..2^28 points and triangles, got (%r, %r, %r)"
-                         % (B, N, T))
-    return dict(zip(("splits", "queries_per_lane", "triangle_tile", "workgroup_size"), list(out)))
+    return _plan("nearest_triangle_plan", (B, N, T),
+                 ("splits", "queries_per_lane", "triangle_tile", "workgroup_size"),
+                 "1..65535 images of 1..2^28 points and triangles")
 
 
 def _chk_point_mesh(points, vertices, triangles, lengths):
@@ -1334,13 +1334,9 @@ def nearest_triangle_backward(points, vertices, triangles, lengths, face, bary, 
 def nearest_point_of_triangle_plan(B, N, T):
     """The launch shape mr_nearest_point_of_triangle_forward takes for B images of T triangles against N points, a
     pure host function: {"splits", "points_per_step", "point_tile", "workgroup_size"} (include/mesh_raster.h)."""
-    out = (ctypes.c_int * 4)()
-    rc = lib().mr_nearest_point_of_triangle_plan(int(B), int(N), int(T),
-                                                 *[ctypes.c_void_p(ctypes.addressof(out) + 4 * k) for k in range(4)])
-    if rc != MR_OK:
-        raise ValueError("nearest_point_of_triangle_plan takes 1..65535 images of 1..2^28 points and triangles, got "
-                         "(%r, %r, %r)" % (B, N, T))
-    return dict(zip(("splits", "points_per_step", "point_tile", "workgroup_size"), list(out)))
+    return _plan("nearest_point_of_triangle_plan", (B, N, T),
+                 ("splits", "points_per_step", "point_tile", "workgroup_size"),
+                 "1..65535 images of 1..2^28 points and triangles")
 
 
 def nearest_point_of_triangle_forward(points, vertices, triangles, lengths=None, want_sqdist=True, want_total=False):

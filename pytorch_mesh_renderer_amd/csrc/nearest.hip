@@ -11,24 +11,13 @@
 // fused multiply-adds, a compare and two selects per (query, target) pair -- the first six in packed fp32, two
 // queries an instruction, where a lane holds four queries -- and no memory traffic to speak of.
 //
-// Forward: a lane keeps `queries_per_lane` queries and their running (best distance, best index) in registers; a
-// workgroup stages 256 targets at a time in LDS as three planes and every lane reads the same four targets per
-// ds_read_b128 (one address for the wavefront: a broadcast).  The grid is (query blocks, target splits, B): with few
-// queries and many targets -- a mesh's vertices against a scan -- the target range is cut into `splits` runs of whole
-// tiles so that the chip is filled (nearest_plan, a pure host function).  A split writes one 64-bit key per query,
-// (distance bits << 32) | index, to a slot of its own with a plain store; k_nearest_merge takes the unsigned minimum
-// over a query's slots.  Distances are >= 0, so their bit patterns order like the values, and the index in the low
-// word sends equal distances to the lowest index whatever the launch shape: no atomics, no dependence on the order
-// in which workgroups finish.  Inside a split the targets are visited in ascending order with a strict '<'.
-// Chamfer's per-image mean is a fixed-order sum: the pass that writes the final distances also sums its workgroup's
-// into one workspace float, and k_nearest_mean adds an image's floats in a fixed order (as k_mesh_reg_sum_rows).
-//
-// Backward of sum_i g_i |x_i - y_idx_i|^2: a gather half, dx_i = 2 g_i (x_i - y_idx_i), and a scatter half,
-// dy_j = -sum_{i: idx_i = j} 2 g_i (x_i - y_j).  The scatter runs as a gather over an inverted index built from the
-// saved idx (the caller's stable sort: per destination, its queries in ascending order): eight lanes own one
-// destination point, walk its list eight entries a trip and meet in a fixed butterfly.  One launch per cloud writes
-// every gradient row exactly once -- both halves that land on it, when Chamfer runs both directions -- so nothing is
-// zero-filled and the result is bitwise reproducible in either deterministic mode.
+// Every search has one frame, and each piece of it stands once, under "the searches' frame" below: a lane keeps its
+// queries and their running result in registers (load_queries), a workgroup stages a tile of targets in LDS
+// (stage_points) and every lane reads the same targets from it (read_targets), the target range is cut
+// into splits that fill the chip (plan_of, split_range) and meet through 64-bit keys (key_of, k_nearest_merge), and
+// the pass that writes the final distances sums them for the mean (store_partial, k_nearest_mean).  Every backward
+// has one frame too: eight lanes per gradient row (gather_rows).  Neither uses an atomic, so every result is bitwise
+// reproducible whatever the launch shape, in either deterministic mode.
 #include <math.h>
 
 #include "mr_internal.h"
@@ -45,6 +34,10 @@ constexpr int kPointsPerBlock = kThreads / kLanesPerPoint;
 static_assert(kThreads == 4 * kWave, "block_sum sums four wavefronts");
 static_assert(kTile % 4 == 0, "the tile is read four targets at a time");
 
+// ---- the searches' frame: host side -----------------------------------------------------------------------------
+// The grid of a search is (query blocks, target splits, B): with few queries and many targets -- a mesh's vertices
+// against a scan -- the target range is cut into `splits` runs of whole tiles so that the chip is filled (the
+// *_plan functions, pure host functions).
 struct Plan {
   int splits, queries_per_lane, query_blocks, chunk;   // chunk: targets per split, whole tiles
 };
@@ -67,47 +60,144 @@ inline Plan plan_of(int B, int N, int M, int tile = kTile, int wide = kWideQueri
   return p;
 }
 
-inline unsigned merge_blocks_of(int N) { return (unsigned)((N + kThreads - 1) / kThreads); }
-
-// rows of the last pass over the queries (the one that writes the distances): what k_nearest_mean adds per image
-inline unsigned partial_rows_of(const Plan &p, int N) {
-  return p.splits > 1 ? merge_blocks_of(N) : (unsigned)p.query_blocks;
+inline dim3 search_grid(const Plan &p, int B) {
+  return dim3((unsigned)p.query_blocks, (unsigned)p.splits, (unsigned)B);
 }
 
-inline size_t keys_bytes(const Plan &p, int B, int N) {
-  return p.splits > 1 ? align_up((size_t)B * p.splits * N * sizeof(unsigned long long), 256) : 0;
+// one thread per row of n (the merge and finish passes), and eight lanes per row of n (gather_rows)
+inline unsigned row_blocks_of(int n) { return (unsigned)((n + kThreads - 1) / kThreads); }
+inline dim3 rows_grid(int n, int B) { return dim3(row_blocks_of(n), (unsigned)B); }
+inline dim3 groups_grid(int n, int B) {
+  return dim3((unsigned)((n + kPointsPerBlock - 1) / kPointsPerBlock), (unsigned)B);
 }
 
+// A search's workspace: the triangle records | the splits' keys (splits > 1) | the partial sums of the last pass
+// over the queries.  Byte offsets and the size; *_ws() and launch_*_forward() both take them from here.
+struct Layout {
+  size_t records, keys, partials, bytes;
+};
+
+struct Workspace {
+  float4 *records;
+  unsigned long long *keys;   // null without a split
+  float *partials;            // null when no total is wanted
+};
+
+inline Layout layout_of(const Plan &p, int B, size_t records_bytes, size_t keys_per_split, size_t partial_rows) {
+  Layout l;
+  l.records = 0;
+  l.keys = l.records + records_bytes;
+  l.partials =
+      l.keys + (p.splits > 1 ? align_up((size_t)B * p.splits * keys_per_split * sizeof(unsigned long long), 256) : 0);
+  l.bytes = l.partials + align_up((size_t)B * partial_rows * sizeof(float), 256);
+  return l;
+}
+
+inline Workspace carve(void *ws, const Plan &p, const Layout &l, bool want_partials) {
+  Workspace w;
+  w.records = (float4 *)((char *)ws + l.records);
+  w.keys = p.splits > 1 ? (unsigned long long *)((char *)ws + l.keys) : nullptr;
+  w.partials = want_partials ? (float *)((char *)ws + l.partials) : nullptr;
+  return w;
+}
+
+// ---- the searches' frame: device side ---------------------------------------------------------------------------
 __device__ __forceinline__ int valid_count(const int32_t *__restrict__ lengths, int b, int n) {
   return lengths ? min(max(lengths[b], 0), n) : n;
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) {
 #pragma unroll
   for (int m = 1; m < kWave; m <<= 1) v += __shfl_xor(v, m, kWave);
   return v;
 }
 
 // The workgroup's sum of v in a fixed order, returned on every thread.  Every thread of the workgroup calls it.
-__device__ __forceinline__ float block_sum(float v) {
-  __shared__ float part[kThreads / kWave];
+template <typename T>
+__device__ __forceinline__ T block_sum(T v) {
+  __shared__ T part[kThreads / kWave];
   v = wave_sum(v);
   if (lane_id() == 0) part[(int)threadIdx.x / kWave] = v;
   __syncthreads();
   return (part[0] + part[1]) + (part[2] + part[3]);
 }
 
-// The sum of v over the eight lanes that own one destination row, in a fixed butterfly, on each of them.
-__device__ __forceinline__ float group_sum(float v) {
-#pragma unroll
-  for (int m = 1; m < kLanesPerPoint; m <<= 1) v += __shfl_xor(v, m, kLanesPerPoint);
-  return v;
+// Chamfer's per-image mean is a fixed-order sum: the pass that writes the final distances also sums its workgroup's
+// into partials[b, blockIdx.x], and k_nearest_mean adds an image's floats in a fixed order (as k_mesh_reg_sum_rows).
+// Every thread of the workgroup calls it; nothing happens without partials (a kernel argument: the same on every
+// thread).
+__device__ __forceinline__ void store_partial(float *__restrict__ partials, int b, float v) {
+  if (!partials) return;
+  v = block_sum(v);
+  if (threadIdx.x == 0) partials[(size_t)b * gridDim.x + blockIdx.x] = v;
 }
 
+// A split writes one 64-bit key per query, (distance bits << 32) | index, to a slot of its own with a plain store;
+// the merge takes the unsigned minimum over a query's slots.  Distances are >= 0, so their bit patterns order like
+// the values, and the index in the low word sends equal distances to the lowest index whatever the launch shape: no
+// atomics, no dependence on the order in which workgroups finish.  A NaN's bit pattern is above +inf's.
 constexpr unsigned long long kNoKey = ~0ull;
+__device__ __forceinline__ unsigned long long key_of(float d, int j) {
+  return ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)j;
+}
+__device__ __forceinline__ float key_distance(unsigned long long key) { return __uint_as_float((unsigned)(key >> 32)); }
+__device__ __forceinline__ int key_index(unsigned long long key) { return (int)(unsigned)(key & 0xffffffffull); }
+
+// The targets [j0, j1) of split `split` among the image's n, maybe none; the same on every thread.
+struct Range {
+  int j0, j1;
+};
+__device__ __forceinline__ Range split_range(int split, int chunk, int n) {
+  const int j0 = min(split * chunk, n);
+  return Range{j0, min(j0 + chunk, n)};
+}
+
+// The Q queries of a lane, i0 + q kThreads of the image's points xb; zero for a padded row.
+template <int Q>
+__device__ __forceinline__ void load_queries(const float *__restrict__ xb, int i0, int nv, float (&px)[Q],
+                                             float (&py)[Q], float (&pz)[Q]) {
+#pragma unroll
+  for (int q = 0; q < Q; ++q) {
+    const int i = i0 + q * kThreads;
+    const bool have = i < nv;
+    px[q] = have ? xb[3 * (size_t)i] : 0.0f;
+    py[q] = have ? xb[3 * (size_t)i + 1] : 0.0f;
+    pz[q] = have ? xb[3 * (size_t)i + 2] : 0.0f;
+  }
+}
+
+// `count` points from src into the three LDS planes, `fill` from there up to `padded`.  Every thread of the
+// workgroup calls it with the same arguments; the planes are the workgroup's to read when it returns.
+__device__ __forceinline__ void stage_points(const float *__restrict__ src, int count, int padded, float fill,
+                                             float *sx, float *sy, float *sz) {
+  __syncthreads();
+  for (int f = (int)threadIdx.x; f < 3 * padded; f += kThreads) {
+    const int j = f / 3, c = f - 3 * j;
+    const float v = j < count ? src[f] : fill;
+    float *plane = c == 0 ? sx : (c == 1 ? sy : sz);
+    plane[j] = v;
+  }
+  __syncthreads();
+}
+
+// The staged targets j .. j + 3 (j a multiple of four): every lane reads the same four targets per ds_read_b128 (one
+// address for the wavefront: a broadcast).
+__device__ __forceinline__ void read_targets(const float *sx, const float *sy, const float *sz, int j, float (&ax)[4],
+                                             float (&ay)[4], float (&az)[4]) {
+  const float4 tx = *reinterpret_cast<const float4 *>(&sx[j]);
+  const float4 ty = *reinterpret_cast<const float4 *>(&sy[j]);
+  const float4 tz = *reinterpret_cast<const float4 *>(&sz[j]);
+  ax[0] = tx.x, ax[1] = tx.y, ax[2] = tx.z, ax[3] = tx.w;
+  ay[0] = ty.x, ay[1] = ty.y, ay[2] = ty.z, ay[3] = ty.w;
+  az[0] = tz.x, az[1] = tz.y, az[2] = tz.z, az[3] = tz.w;
+}
+
 typedef float F2 __attribute__((ext_vector_type(2)));
 
 // ---- forward ----------------------------------------------------------------------------------------------------
+// A lane keeps Q queries and their running (best distance, best index) in registers; a workgroup stages 256 targets
+// at a time.  Inside a split the targets are visited in ascending order with a strict '<'.
 // grid (query blocks, splits, B).  keys != null (splits > 1): one key per (image, split, query) and nothing else;
 // keys == null: the final sqdist / idx and, with partials, the workgroup's sum of its valid distances.
 template <int Q>
@@ -122,42 +212,26 @@ __global__ __launch_bounds__(kThreads) void k_nearest(const float *__restrict__ 
   __shared__ __attribute__((aligned(16))) float sz[kTile];
   const int b = (int)blockIdx.z, split = (int)blockIdx.y;
   const int nv = valid_count(x_lengths, b, N), mv = valid_count(y_lengths, b, M);
-  const float *xb = x + (size_t)b * N * 3;
   const float *yb = y + (size_t)b * M * 3;
-  const int j0 = min(split * chunk, mv), j1 = min(j0 + chunk, mv);   // this split's targets, maybe none
+  const Range run = split_range(split, chunk, mv);
   const int i0 = (int)blockIdx.x * (kThreads * Q) + (int)threadIdx.x;
 
   float px[Q], py[Q], pz[Q], best[Q];
   int bi[Q];
+  load_queries<Q>(x + (size_t)b * N * 3, i0, nv, px, py, pz);
 #pragma unroll
   for (int q = 0; q < Q; ++q) {
-    const int i = i0 + q * kThreads;
-    const bool have = i < nv;
-    px[q] = have ? xb[3 * (size_t)i] : 0.0f;
-    py[q] = have ? xb[3 * (size_t)i + 1] : 0.0f;
-    pz[q] = have ? xb[3 * (size_t)i + 2] : 0.0f;
     best[q] = INFINITY;
-    bi[q] = j0;   // what a query whose every distance is NaN keeps: in range wherever the split has a target
+    bi[q] = run.j0;   // what a query whose every distance is NaN keeps: in range wherever the split has a target
   }
 
-  for (int t0 = j0; t0 < j1; t0 += kTile) {   // j0, j1: the same on every thread
-    const int count = min(kTile, j1 - t0);
+  for (int t0 = run.j0; t0 < run.j1; t0 += kTile) {
+    const int count = min(kTile, run.j1 - t0);
     const int padded = (count + 3) & ~3;   // +inf beyond count: never nearer than anything
-    __syncthreads();
-    for (int f = (int)threadIdx.x; f < 3 * padded; f += kThreads) {
-      const int j = f / 3, c = f - 3 * j;
-      const float v = j < count ? yb[3 * (size_t)t0 + f] : INFINITY;
-      float *plane = c == 0 ? sx : (c == 1 ? sy : sz);
-      plane[j] = v;
-    }
-    __syncthreads();
+    stage_points(yb + 3 * (size_t)t0, count, padded, INFINITY, sx, sy, sz);
     for (int j = 0; j < padded; j += 4) {
-      const float4 tx = *reinterpret_cast<const float4 *>(&sx[j]);
-      const float4 ty = *reinterpret_cast<const float4 *>(&sy[j]);
-      const float4 tz = *reinterpret_cast<const float4 *>(&sz[j]);
-      const float ax[4] = {tx.x, tx.y, tx.z, tx.w};
-      const float ay[4] = {ty.x, ty.y, ty.z, ty.w};
-      const float az[4] = {tz.x, tz.y, tz.z, tz.w};
+      float ax[4], ay[4], az[4];
+      read_targets(sx, sy, sz, j, ax, ay, az);
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         if constexpr (Q % 2 == 0) {
@@ -197,9 +271,7 @@ __global__ __launch_bounds__(kThreads) void k_nearest(const float *__restrict__ 
     const int i = i0 + q * kThreads;
     if (i >= N) continue;
     if (keys) {
-      const unsigned long long key =
-          (i < nv && j0 < j1) ? ((unsigned long long)__float_as_uint(best[q]) << 32) | (unsigned)bi[q] : kNoKey;
-      keys[((size_t)b * gridDim.y + split) * N + i] = key;
+      keys[((size_t)b * gridDim.y + split) * N + i] = (i < nv && run.j0 < run.j1) ? key_of(best[q], bi[q]) : kNoKey;
     } else {
       const bool valid = i < nv && mv > 0;
       const float d = valid ? best[q] : 0.0f;
@@ -208,10 +280,7 @@ __global__ __launch_bounds__(kThreads) void k_nearest(const float *__restrict__ 
       sum += d;
     }
   }
-  if (partials) {   // (a kernel argument: the same on every thread)
-    sum = block_sum(sum);
-    if (threadIdx.x == 0) partials[(size_t)b * gridDim.x + blockIdx.x] = sum;
-  }
+  store_partial(partials, b, sum);
 }
 
 // The unsigned minimum of a query's keys over the splits -> sqdist, idx and the workgroup's partial sum.
@@ -232,14 +301,11 @@ __global__ __launch_bounds__(kThreads) void k_nearest_merge(const unsigned long 
       key = k < key ? k : key;
     }
     const bool valid = i < nv && mv > 0 && key != kNoKey;
-    d = valid ? __uint_as_float((unsigned)(key >> 32)) : 0.0f;
+    d = valid ? key_distance(key) : 0.0f;
     if (sqdist) sqdist[(size_t)b * N + i] = d;
-    idx[(size_t)b * N + i] = valid ? min(max((int)(unsigned)(key & 0xffffffffull), 0), mv - 1) : -1;
+    idx[(size_t)b * N + i] = valid ? min(max(key_index(key), 0), mv - 1) : -1;
   }
-  if (partials) {
-    d = block_sum(d);
-    if (threadIdx.x == 0) partials[(size_t)b * gridDim.x + blockIdx.x] = d;
-  }
+  store_partial(partials, b, d);
 }
 
 // total[b] (+)= weight * (the sum of image b's `count` partials in a fixed order) / its valid queries; a direction
@@ -261,6 +327,11 @@ __global__ __launch_bounds__(kThreads) void k_nearest_mean(const float *__restri
 }
 
 // ---- backward ---------------------------------------------------------------------------------------------------
+// Backward of sum_i g_i |x_i - y_idx_i|^2: a gather half, dx_i = 2 g_i (x_i - y_idx_i), and a scatter half,
+// dy_j = -sum_{i: idx_i = j} 2 g_i (x_i - y_j).  The scatter runs as a gather over an inverted index built from the
+// saved idx (the caller's stable sort: per destination, its queries in ascending order).  One launch per cloud
+// writes every gradient row exactly once -- both halves that land on it, when Chamfer runs both directions -- so
+// nothing is zero-filled and the result is bitwise reproducible in either deterministic mode.
 struct V3 {
   float x, y, z;
 };
@@ -271,6 +342,28 @@ struct Upstream {
   float per_image;                    // used when points is null
   __device__ __forceinline__ float at(size_t i) const { return points ? points[i] : per_image; }
 };
+
+// The sum of v over the eight lanes that own one destination row, in a fixed butterfly, on each of them.
+__device__ __forceinline__ float group_sum(float v) {
+#pragma unroll
+  for (int m = 1; m < kLanesPerPoint; m <<= 1) v += __shfl_xor(v, m, kLanesPerPoint);
+  return v;
+}
+
+// The frame of every gather: out[b, row] = the sum over sub of what body(row, sub, dx, dy, dz) adds to (dx, dy, dz),
+// for the image's `rows` rows.  Eight lanes (sub 0 .. 7) own one row, walk its list eight entries a trip -- for
+// (k = e0 + sub; k < e1; k += kLanesPerPoint) -- and meet in a fixed butterfly; whole groups of eight either have a
+// row or do not, so the butterfly stays inside one.  grid (ceil(rows / kPointsPerBlock), B)
+template <typename Body>
+__device__ __forceinline__ void gather_rows(int b, int rows, V3 *__restrict__ out, Body body) {
+  const int row = (int)blockIdx.x * kPointsPerBlock + (int)threadIdx.x / kLanesPerPoint;
+  const int sub = (int)threadIdx.x % kLanesPerPoint;
+  const bool have = row < rows;
+  float dx = 0.0f, dy = 0.0f, dz = 0.0f;
+  if (have) body(row, sub, dx, dy, dz);
+  dx = group_sum(dx), dy = group_sum(dy), dz = group_sum(dz);
+  if (have && sub == 0) out[(size_t)b * rows + row] = V3{dx, dy, dz};
+}
 
 // dp[b, p] for one cloud p (Np points) against the other cloud o (No points): the gather half of the direction
 // p -> o (idx_po, null when that direction did not run) plus the scatter half of the direction o -> p through its
@@ -283,16 +376,13 @@ __global__ __launch_bounds__(kThreads) void k_nearest_backward(
     const int32_t *__restrict__ offsets_op, const float *__restrict__ g_points_op, float weight_op,
     const float *__restrict__ g_images, V3 *__restrict__ dp) {
   const int b = (int)blockIdx.y;
-  const int p = (int)blockIdx.x * kPointsPerBlock + (int)threadIdx.x / kLanesPerPoint;
-  const int sub = (int)threadIdx.x % kLanesPerPoint;
-  const bool have = p < Np;   // (whole groups of eight: the butterfly below stays inside one)
   const int pv = valid_count(p_lengths, b, Np), ov = valid_count(o_lengths, b, No);
   const float gi = g_images ? g_images[b] : 0.0f;   // b = blockIdx.y: wave-uniform
   const Upstream up_po{g_points_po, pv > 0 ? gi * weight_po / (float)pv : 0.0f};
   const Upstream up_op{g_points_op, ov > 0 ? gi * weight_op / (float)ov : 0.0f};
   const V3 *ob = o_points + (size_t)b * No;
-  float dx = 0.0f, dy = 0.0f, dz = 0.0f;
-  if (have && p < pv) {
+  gather_rows(b, Np, dp, [&](int p, int sub, float &dx, float &dy, float &dz) {
+    if (p >= pv) return;
     const V3 me = p_points[(size_t)b * Np + p];
     if (idx_po && sub == 0) {
       const int j = idx_po[(size_t)b * Np + p];
@@ -317,9 +407,7 @@ __global__ __launch_bounds__(kThreads) void k_nearest_backward(
         dz += g2 * (me.z - o.z);
       }
     }
-  }
-  dx = group_sum(dx), dy = group_sum(dy), dz = group_sum(dz);
-  if (have && sub == 0) dp[(size_t)b * Np + p] = V3{dx, dy, dz};
+  });
 }
 
 // ---- point to triangle ------------------------------------------------------------------------------------------
@@ -343,7 +431,7 @@ __global__ __launch_bounds__(kThreads) void k_nearest_backward(
 //
 // Backward (the envelope theorem: the barycentrics are constants): dp_i = 2 g_i (p_i - c_i), one row per query, and
 // dv_k = -sum 2 g_i bary_ik (p_i - c_i) as a gather over the inverted index of the 3N (query, corner) entries keyed
-// by vertex, eight lanes per vertex and the butterfly of k_nearest_backward; p - c is d - (beta e0 + gamma e1) again.
+// by vertex (gather_rows: eight lanes per vertex); p - c is d - (beta e0 + gamma e1) again.
 constexpr int kTriTile = 128;          // records staged in LDS at a time (10 KB), and the granularity of a split
 constexpr int kTriWideQueries = 2;     // queries per lane once a cloud fills a workgroup of them: one packed pair
 constexpr int kRecWords = 5;           // 16-byte words per record
@@ -413,6 +501,13 @@ __device__ __forceinline__ F tri_distance(const Candidates<F> &c) {
   return lesser(c.ca, lesser(c.bc, lesser(c.ab, lesser(c.inside, (F)INFINITY))));
 }
 
+// Triangle t's three indices; true when it is usable: all of them in [0, V).
+__device__ __forceinline__ bool usable_triangle(const int32_t *__restrict__ triangles, int t, int V, int &ia, int &ib,
+                                                int &ic) {
+  ia = triangles[3 * (size_t)t], ib = triangles[3 * (size_t)t + 1], ic = triangles[3 * (size_t)t + 2];
+  return (unsigned)ia < (unsigned)V && (unsigned)ib < (unsigned)V && (unsigned)ic < (unsigned)V;
+}
+
 // grid (ceil(T / kThreads), B): records [B, T, kRecWords] of 16-byte words
 __global__ __launch_bounds__(kThreads) void k_nt_setup(const V3 *__restrict__ vertices,
                                                        const int32_t *__restrict__ triangles, int V, int T,
@@ -420,9 +515,9 @@ __global__ __launch_bounds__(kThreads) void k_nt_setup(const V3 *__restrict__ ve
   const int b = (int)blockIdx.y, t = (int)blockIdx.x * kThreads + (int)threadIdx.x;
   if (t >= T) return;
   float4 *out = records + ((size_t)b * T + t) * kRecWords;
-  const int ia = triangles[3 * (size_t)t], ib = triangles[3 * (size_t)t + 1], ic = triangles[3 * (size_t)t + 2];
+  int ia, ib, ic;
   const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-  if ((unsigned)ia >= (unsigned)V || (unsigned)ib >= (unsigned)V || (unsigned)ic >= (unsigned)V) {
+  if (!usable_triangle(triangles, t, V, ia, ib, ic)) {
     out[0] = make_float4(INFINITY, INFINITY, INFINITY, 0.0f);   // d = p - a is -inf or NaN: never below the best
     out[1] = out[2] = out[3] = out[4] = zero;
     return;
@@ -456,35 +551,31 @@ __global__ __launch_bounds__(kThreads) void k_nt_search(const float *__restrict_
   __shared__ float4 tile[kTriTile * kRecWords];
   const int b = (int)blockIdx.z, split = (int)blockIdx.y;
   const int nv = valid_count(lengths, b, N);
-  const float *pb = points + (size_t)b * N * 3;
   const float4 *rb = records + (size_t)b * T * kRecWords;
-  const int j0 = min(split * chunk, T), j1 = min(j0 + chunk, T);
+  const Range run = split_range(split, chunk, T);
   const int i0 = (int)blockIdx.x * (kThreads * Q) + (int)threadIdx.x;
 
-  float p[3][Q], best[Q];
+  float qx[Q], qy[Q], qz[Q], best[Q];
   int bi[Q];
+  load_queries<Q>(points + (size_t)b * N * 3, i0, nv, qx, qy, qz);
 #pragma unroll
   for (int q = 0; q < Q; ++q) {
-    const int i = i0 + q * kThreads;
-    const bool have = i < nv;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) p[c][q] = have ? pb[3 * (size_t)i + c] : 0.0f;
     best[q] = INFINITY;
     bi[q] = -1;
   }
   F px, py, pz;
   if constexpr (Q == 2) {
-    px = F{p[0][0], p[0][1]};
-    py = F{p[1][0], p[1][1]};
-    pz = F{p[2][0], p[2][1]};
+    px = F{qx[0], qx[1]};
+    py = F{qy[0], qy[1]};
+    pz = F{qz[0], qz[1]};
   } else {
-    px = p[0][0];
-    py = p[1][0];
-    pz = p[2][0];
+    px = qx[0];
+    py = qy[0];
+    pz = qz[0];
   }
 
-  for (int t0 = j0; t0 < j1; t0 += kTriTile) {   // j0, j1: the same on every thread
-    const int count = min(kTriTile, j1 - t0);
+  for (int t0 = run.j0; t0 < run.j1; t0 += kTriTile) {
+    const int count = min(kTriTile, run.j1 - t0);
     __syncthreads();
     for (int f = (int)threadIdx.x; f < count * kRecWords; f += kThreads) tile[f] = rb[(size_t)t0 * kRecWords + f];
     __syncthreads();
@@ -508,8 +599,7 @@ __global__ __launch_bounds__(kThreads) void k_nt_search(const float *__restrict_
     if (i >= N) continue;
     const bool found = i < nv && bi[q] >= 0;
     if (keys)
-      keys[((size_t)b * gridDim.y + split) * N + i] =
-          found ? ((unsigned long long)__float_as_uint(best[q]) << 32) | (unsigned)bi[q] : kNoKey;
+      keys[((size_t)b * gridDim.y + split) * N + i] = found ? key_of(best[q], bi[q]) : kNoKey;
     else
       face[(size_t)b * N + i] = found ? bi[q] : -1;
   }
@@ -530,45 +620,42 @@ __device__ __forceinline__ bool nt_evaluate(V3 p, const float4 *__restrict__ r, 
   return d < INFINITY;
 }
 
-// The chosen face once more, with the search's own functions -> sqdist, the face (-1 for a row without a result),
-// the barycentrics and the workgroup's partial sum.  grid (ceil(N / kThreads), B)
+// The chosen pair of every row once more, with the search's own functions -> sqdist, chosen (-1 for a row without a
+// result), the barycentrics and the workgroup's partial sum.  Point to triangle: the rows are the N points, row i
+// pairs point i with the face chosen[i].  Triangle to point (kRowsAreTriangles): the rows are the T triangles, row i
+// pairs triangle i with the point chosen[i].  The search never names a face or a point outside the image's.
+// grid (ceil(rows / kThreads), B)
+template <bool kRowsAreTriangles>
 __global__ __launch_bounds__(kThreads) void k_nt_finish(const V3 *__restrict__ points,
                                                         const float4 *__restrict__ records,
                                                         const int32_t *__restrict__ lengths, int N, int T,
-                                                        float *__restrict__ sqdist, int32_t *__restrict__ face,
+                                                        float *__restrict__ sqdist, int32_t *__restrict__ chosen,
                                                         V3 *__restrict__ bary, float *__restrict__ partials) {
   const int b = (int)blockIdx.y;
   const int i = (int)blockIdx.x * kThreads + (int)threadIdx.x;
   const int nv = valid_count(lengths, b, N);
+  const int R = kRowsAreTriangles ? T : N;
   float d = 0.0f;
-  if (i < N) {
-    const size_t row = (size_t)b * N + i;
-    int f = i < nv ? face[row] : -1;
-    V3 w = {0.0f, 0.0f, 0.0f};
-    if ((unsigned)f < (unsigned)T) {
-      if (!nt_evaluate(points[row], records + ((size_t)b * T + f) * kRecWords, d, w))
-        f = -1;   // (the search never names such a face)
-    } else {
-      f = -1;
-    }
-    if (f < 0) {
+  if (i < R) {
+    const size_t row = (size_t)b * R + i;
+    int c = (kRowsAreTriangles || i < nv) ? chosen[row] : -1;
+    const int point = kRowsAreTriangles ? c : i, f = kRowsAreTriangles ? i : c;
+    V3 w;
+    if ((unsigned)c >= (unsigned)(kRowsAreTriangles ? nv : T) ||
+        !nt_evaluate(points[(size_t)b * N + point], records + ((size_t)b * T + f) * kRecWords, d, w)) {
+      c = -1;
       d = 0.0f;
       w = V3{0.0f, 0.0f, 0.0f};
     }
     if (sqdist) sqdist[row] = d;
-    face[row] = f;
+    chosen[row] = c;
     bary[row] = w;
   }
-  if (partials) {   // (a kernel argument: the same on every thread)
-    d = block_sum(d);
-    if (threadIdx.x == 0) partials[(size_t)b * gridDim.x + blockIdx.x] = d;
-  }
+  store_partial(partials, b, d);
 }
 
-// p - c = d - (beta e0 + gamma e1) of the pair that row i of a saved result names, and the row's weights.  Point to
-// triangle: the rows are the points, row i pairs point i with the face chosen[i].  Triangle to point
-// (kRowsAreTriangles, i < T): the rows are the triangles, row i pairs triangle i with the point chosen[i].  pv: the
-// image's valid points.  False for a row without a result.
+// p - c = d - (beta e0 + gamma e1) of the pair that row i of a saved result names (the rows: as k_nt_finish's), and
+// the row's weights.  pv: the image's valid points.  False for a row without a result.
 template <bool kRowsAreTriangles>
 __device__ __forceinline__ bool nt_residual(const V3 *__restrict__ pb, const V3 *__restrict__ vb,
                                             const int32_t *__restrict__ triangles, const int32_t *__restrict__ cb,
@@ -582,8 +669,8 @@ __device__ __forceinline__ bool nt_residual(const V3 *__restrict__ pb, const V3 
     f = cb[i];
     if ((unsigned)f >= (unsigned)T) return false;
   }
-  const int ia = triangles[3 * (size_t)f], ib = triangles[3 * (size_t)f + 1], ic = triangles[3 * (size_t)f + 2];
-  if ((unsigned)ia >= (unsigned)V || (unsigned)ib >= (unsigned)V || (unsigned)ic >= (unsigned)V) return false;
+  int ia, ib, ic;
+  if (!usable_triangle(triangles, f, V, ia, ib, ic)) return false;
   const V3 p = pb[point], a = vb[ia], e = vb[ib], c = vb[ic];
   w = wb[i];
   r.x = (p.x - a.x) - (w.y * (e.x - a.x) + w.z * (c.x - a.x));
@@ -615,8 +702,8 @@ __global__ __launch_bounds__(kThreads) void k_nt_backward_points(
 // dvertices[b, v] = -sum over the (row, corner) entries that name v of 2 g_i bary_ik (p - c)_i: with R rows (the N
 // points, or with kRowsAreTriangles the T triangles: nt_residual) order [B, 3R] holds the entries 3 i + k grouped by
 // vertex, each group ascending, offsets [B, V + 1]; chosen, bary and g_rows are [B, R, ...].  The mean's upstream is
-// g_images[b] over the image's valid points, with triangle rows over divisors[b] (its usable triangles).  Eight
-// lanes per vertex.  grid (ceil(V / kPointsPerBlock), B)
+// g_images[b] over the image's valid points, with triangle rows over divisors[b] (its usable triangles).
+// grid (ceil(V / kPointsPerBlock), B)
 template <bool kRowsAreTriangles>
 __global__ __launch_bounds__(kThreads) void k_nt_backward_vertices(
     const V3 *__restrict__ points, const V3 *__restrict__ vertices, const int32_t *__restrict__ triangles,
@@ -625,15 +712,11 @@ __global__ __launch_bounds__(kThreads) void k_nt_backward_vertices(
     const float *__restrict__ g_rows, const float *__restrict__ g_images, const int32_t *__restrict__ divisors,
     V3 *__restrict__ dvertices) {
   const int b = (int)blockIdx.y;
-  const int v = (int)blockIdx.x * kPointsPerBlock + (int)threadIdx.x / kLanesPerPoint;
-  const int sub = (int)threadIdx.x % kLanesPerPoint;
-  const bool have = v < V;   // (whole groups of eight: the butterfly below stays inside one)
   const int R = kRowsAreTriangles ? T : N;
   const int nv = valid_count(lengths, b, N);
   const int count = kRowsAreTriangles ? (g_images ? divisors[b] : 0) : nv;
   const Upstream up{g_rows, (g_images && count > 0) ? g_images[b] / (float)count : 0.0f};
-  float dx = 0.0f, dy = 0.0f, dz = 0.0f;
-  if (have) {
+  gather_rows(b, V, dvertices, [&](int v, int sub, float &dx, float &dy, float &dz) {
     const int32_t *off = offsets + (size_t)b * (V + 1);
     const int e0 = max(off[v], 0), e1 = min(off[v + 1], 3 * R);
     for (int k = e0 + sub; k < e1; k += kLanesPerPoint) {
@@ -649,9 +732,7 @@ __global__ __launch_bounds__(kThreads) void k_nt_backward_vertices(
       dy += s * r.y;
       dz += s * r.z;
     }
-  }
-  dx = group_sum(dx), dy = group_sum(dy), dz = group_sum(dz);
-  if (have && sub == 0) dvertices[(size_t)b * V + v] = V3{dx, dy, dz};
+  });
 }
 
 // ---- triangle to point ------------------------------------------------------------------------------------------
@@ -666,8 +747,8 @@ __global__ __launch_bounds__(kThreads) void k_nt_backward_vertices(
 // lower half first), so the lowest point of equal distances wins; NaN and +inf never do; an odd last point shares
 // its pair with a +inf point written into the tile.  The grid is (triangle blocks, splits, B): plan_of with the
 // triangles as the queries cuts the CLOUD into `splits` runs of whole tiles, which meet through the 64-bit keys and
-// k_nearest_merge.  k_tp_finish is k_nt_finish for triangle rows (nt_evaluate), the mean is k_nearest_mean over its
-// partial sums with the divisor k_tp_usable counted: the usable triangles, a property of the topology.
+// k_nearest_merge.  The finish is k_nt_finish with triangle rows, the mean is k_nearest_mean over its partial sums
+// with the divisor k_tp_usable counted: the usable triangles, a property of the topology.
 //
 // Backward: dv_k = -sum 2 g_t bary_tk (p_j(t) - c_t) is k_nt_backward_vertices with triangle rows, a gather over
 // the inverted index of the 3T (triangle, corner) entries keyed by vertex; dp_j = sum_{t: index_t = j} 2 g_t
@@ -676,20 +757,16 @@ constexpr int kPointTile = 256;        // points staged in LDS at a time (3 KB),
 constexpr int kPackedFrom = kPointTile;   // clouds of at least a tile are searched two points a step
 static_assert(kPointTile % 2 == 0, "an odd count is padded to a pair inside the tile");
 
-// U, the triangles with every index in [0, V), into counts[0 .. B).  One workgroup.
+// U, the usable triangles, into counts[0 .. B).  One workgroup.
 __global__ __launch_bounds__(kThreads) void k_tp_usable(const int32_t *__restrict__ triangles, int V, int T, int B,
                                                         int32_t *__restrict__ counts) {
-  __shared__ int part[kThreads / kWave];
   int n = 0;
+#pragma clang loop vectorize(disable) interleave(disable)   // one small pass: two triangles a trip buys nothing
   for (int t = (int)threadIdx.x; t < T; t += kThreads) {
-    const int ia = triangles[3 * (size_t)t], ib = triangles[3 * (size_t)t + 1], ic = triangles[3 * (size_t)t + 2];
-    n += ((unsigned)ia < (unsigned)V && (unsigned)ib < (unsigned)V && (unsigned)ic < (unsigned)V) ? 1 : 0;
+    int ia, ib, ic;
+    n += usable_triangle(triangles, t, V, ia, ib, ic) ? 1 : 0;
   }
-#pragma unroll
-  for (int m = 1; m < kWave; m <<= 1) n += __shfl_xor(n, m, kWave);
-  if (lane_id() == 0) part[(int)threadIdx.x / kWave] = n;
-  __syncthreads();
-  const int total = (part[0] + part[1]) + (part[2] + part[3]);
+  const int total = block_sum(n);
   for (int b = (int)threadIdx.x; b < B; b += kThreads) counts[b] = total;
 }
 
@@ -708,7 +785,7 @@ __global__ __launch_bounds__(kThreads) void k_tp_search(const float *__restrict_
   const int b = (int)blockIdx.z, split = (int)blockIdx.y;
   const int nv = valid_count(lengths, b, N);
   const float *pb = points + (size_t)b * N * 3;
-  const int j0 = min(split * chunk, nv), j1 = min(j0 + chunk, nv);   // this split's points, maybe none
+  const Range run = split_range(split, chunk, nv);
   const int t = (int)blockIdx.x * kThreads + (int)threadIdx.x;
 
   // a lane beyond T keeps an unusable triangle's record: nothing compares below +inf
@@ -721,17 +798,10 @@ __global__ __launch_bounds__(kThreads) void k_tp_search(const float *__restrict_
   float best = INFINITY;
   int bi = -1;
 
-  for (int t0 = j0; t0 < j1; t0 += kPointTile) {   // j0, j1: the same on every thread
-    const int count = min(kPointTile, j1 - t0);
+  for (int t0 = run.j0; t0 < run.j1; t0 += kPointTile) {
+    const int count = min(kPointTile, run.j1 - t0);
     const int padded = (count + Q - 1) / Q * Q;   // <= kPointTile; +inf beyond count: never nearer than anything
-    __syncthreads();
-    for (int f = (int)threadIdx.x; f < 3 * padded; f += kThreads) {
-      const int j = f / 3, c = f - 3 * j;
-      const float v = j < count ? pb[3 * (size_t)t0 + f] : INFINITY;
-      float *plane = c == 0 ? sx : (c == 1 ? sy : sz);
-      plane[j] = v;
-    }
-    __syncthreads();
+    stage_points(pb + 3 * (size_t)t0, count, padded, INFINITY, sx, sy, sz);
     for (int j = 0; j < padded; j += Q) {
       F px, py, pz;   // one address for the wavefront
       if constexpr (Q == 2) {
@@ -756,45 +826,14 @@ __global__ __launch_bounds__(kThreads) void k_tp_search(const float *__restrict_
 
   if (t >= T) return;
   if (keys)
-    keys[((size_t)b * gridDim.y + split) * T + t] =
-        bi >= 0 ? ((unsigned long long)__float_as_uint(best) << 32) | (unsigned)bi : kNoKey;
+    keys[((size_t)b * gridDim.y + split) * T + t] = bi >= 0 ? key_of(best, bi) : kNoKey;
   else
     index[(size_t)b * T + t] = bi;
 }
 
-// The chosen point once more, with the search's own functions -> sqdist, the point (-1 for a triangle without a
-// result), the barycentrics and the workgroup's partial sum.  grid (ceil(T / kThreads), B)
-__global__ __launch_bounds__(kThreads) void k_tp_finish(const V3 *__restrict__ points,
-                                                        const float4 *__restrict__ records,
-                                                        const int32_t *__restrict__ lengths, int N, int T,
-                                                        float *__restrict__ sqdist, int32_t *__restrict__ index,
-                                                        V3 *__restrict__ bary, float *__restrict__ partials) {
-  const int b = (int)blockIdx.y;
-  const int t = (int)blockIdx.x * kThreads + (int)threadIdx.x;
-  const int nv = valid_count(lengths, b, N);
-  float d = 0.0f;
-  if (t < T) {
-    const size_t row = (size_t)b * T + t;
-    int j = index[row];
-    V3 w = {0.0f, 0.0f, 0.0f};
-    if ((unsigned)j >= (unsigned)nv || !nt_evaluate(points[(size_t)b * N + j], records + row * kRecWords, d, w)) {
-      j = -1;   // (the search never names such a point)
-      d = 0.0f;
-      w = V3{0.0f, 0.0f, 0.0f};
-    }
-    if (sqdist) sqdist[row] = d;
-    index[row] = j;
-    bary[row] = w;
-  }
-  if (partials) {   // (a kernel argument: the same on every thread)
-    d = block_sum(d);
-    if (threadIdx.x == 0) partials[(size_t)b * gridDim.x + blockIdx.x] = d;
-  }
-}
-
 // dpoints[b, j] = sum over the triangles t that chose point j of 2 g_t (p_j - c_t): order [B, T] holds the triangles
 // grouped by their point, each group ascending, offsets [B, N + 1].  A point nobody chose, and a padded one, get 0.
-// Eight lanes per point.  grid (ceil(N / kPointsPerBlock), B)
+// grid (ceil(N / kPointsPerBlock), B)
 __global__ __launch_bounds__(kThreads) void k_tp_backward_points(
     const V3 *__restrict__ points, const V3 *__restrict__ vertices, const int32_t *__restrict__ triangles,
     const int32_t *__restrict__ lengths, int N, int V, int T, const int32_t *__restrict__ index,
@@ -802,14 +841,11 @@ __global__ __launch_bounds__(kThreads) void k_tp_backward_points(
     const float *__restrict__ g_triangles, const float *__restrict__ g_images, const int32_t *__restrict__ divisors,
     V3 *__restrict__ dpoints) {
   const int b = (int)blockIdx.y;
-  const int p = (int)blockIdx.x * kPointsPerBlock + (int)threadIdx.x / kLanesPerPoint;
-  const int sub = (int)threadIdx.x % kLanesPerPoint;
-  const bool have = p < N;   // (whole groups of eight: the butterfly below stays inside one)
   const int nv = valid_count(lengths, b, N);
   const int count = g_images ? divisors[b] : 0;
   const Upstream up{g_triangles, (g_images && count > 0) ? g_images[b] / (float)count : 0.0f};
-  float dx = 0.0f, dy = 0.0f, dz = 0.0f;
-  if (have && p < nv) {
+  gather_rows(b, N, dpoints, [&](int p, int sub, float &dx, float &dy, float &dz) {
+    if (p >= nv) return;
     const int32_t *off = offsets + (size_t)b * (N + 1);
     const int e0 = max(off[p], 0), e1 = min(off[p + 1], T);
     for (int k = e0 + sub; k < e1; k += kLanesPerPoint) {
@@ -824,9 +860,7 @@ __global__ __launch_bounds__(kThreads) void k_tp_backward_points(
       dy += g2 * r.y;
       dz += g2 * r.z;
     }
-  }
-  dx = group_sum(dx), dy = group_sum(dy), dz = group_sum(dz);
-  if (have && sub == 0) dpoints[(size_t)b * N + p] = V3{dx, dy, dz};
+  });
 }
 
 // ---- K nearest neighbours ---------------------------------------------------------------------------------------
@@ -843,21 +877,14 @@ __global__ __launch_bounds__(kThreads) void k_tp_backward_points(
 // multiply-adds so that the scalar and the packed instantiations round alike (as tri_candidates).  A split writes
 // its K keys per query to the workspace, k_knn_merge keeps the K smallest of splits x K with the same list.
 //
-// Backward of sum_ik g_ik |x_i - y_idx_ik|^2: k_nearest_backward's eight lanes per destination row and butterfly;
-// a query's row walks its own K slots, a target's row the inverted index of the flattened [N K] indices (entry e
-// belongs to query e / K).  Slots with idx -1 or a distance that is not finite contribute nothing.
+// Backward of sum_ik g_ik |x_i - y_idx_ik|^2: gather_rows again; a query's row walks its own K slots, a target's
+// row the inverted index of the flattened [N K] indices (entry e belongs to query e / K).  Slots with idx -1 or a
+// distance that is not finite contribute nothing.
 constexpr int kKnnMaxK = 32;
 constexpr int knn_wide_queries(int C) { return C <= 4 ? 4 : (C <= 8 ? 2 : 1); }   // 2 C VGPRs of keys a query
 inline int knn_capacity_of(int K) { return K <= 4 ? 4 : (K <= 8 ? 8 : (K <= 16 ? 16 : 32)); }
 inline Plan knn_plan_of(int B, int N, int M, int K) {
   return plan_of(B, N, M, kTile, knn_wide_queries(knn_capacity_of(K)));
-}
-inline size_t knn_keys_bytes(const Plan &p, int B, int N, int K) {
-  return p.splits > 1 ? align_up((size_t)B * p.splits * N * K * sizeof(unsigned long long), 256) : 0;
-}
-
-__device__ __forceinline__ unsigned long long key_of(float d, int j) {
-  return ((unsigned long long)__float_as_uint(d) << 32) | (unsigned)j;
 }
 
 // The C smallest keys offered so far, ascending; kNoKey where fewer were offered.
@@ -893,9 +920,9 @@ __device__ __forceinline__ F knn_distance(F px, F py, F pz, float ax, float ay, 
 __device__ __forceinline__ void knn_write(unsigned long long key, bool row_valid, int k, int mv,
                                           float *__restrict__ sqdist, int32_t *__restrict__ idx, size_t at) {
   const bool valid = row_valid && k < mv && key != kNoKey;
-  const float d = __uint_as_float((unsigned)(key >> 32));
+  const float d = key_distance(key);
   sqdist[at] = valid ? (d != d ? INFINITY : d) : 0.0f;
-  idx[at] = valid ? min((int)(unsigned)(key & 0xffffffffull), mv - 1) : -1;
+  idx[at] = valid ? min(key_index(key), mv - 1) : -1;
 }
 
 // grid (query blocks, splits, B).  keys != null (splits > 1): K keys per (image, split, query), [B, splits, K, N];
@@ -911,41 +938,23 @@ __global__ __launch_bounds__(kThreads) void k_knn(const float *__restrict__ x, c
   __shared__ __attribute__((aligned(16))) float sz[kTile];
   const int b = (int)blockIdx.z, split = (int)blockIdx.y;
   const int nv = valid_count(x_lengths, b, N), mv = valid_count(y_lengths, b, M);
-  const float *xb = x + (size_t)b * N * 3;
   const float *yb = y + (size_t)b * M * 3;
-  const int j0 = min(split * chunk, mv), j1 = min(j0 + chunk, mv);   // this split's targets, maybe none
+  const Range run = split_range(split, chunk, mv);
   const int i0 = (int)blockIdx.x * (kThreads * Q) + (int)threadIdx.x;
 
   float px[Q], py[Q], pz[Q];
   KeyList<C> list[Q];
+  load_queries<Q>(x + (size_t)b * N * 3, i0, nv, px, py, pz);
 #pragma unroll
-  for (int q = 0; q < Q; ++q) {
-    const int i = i0 + q * kThreads;
-    const bool have = i < nv;
-    px[q] = have ? xb[3 * (size_t)i] : 0.0f;
-    py[q] = have ? xb[3 * (size_t)i + 1] : 0.0f;
-    pz[q] = have ? xb[3 * (size_t)i + 2] : 0.0f;
-    list[q].clear();
-  }
+  for (int q = 0; q < Q; ++q) list[q].clear();
 
-  for (int t0 = j0; t0 < j1; t0 += kTile) {   // j0, j1: the same on every thread
-    const int count = min(kTile, j1 - t0);
+  for (int t0 = run.j0; t0 < run.j1; t0 += kTile) {
+    const int count = min(kTile, run.j1 - t0);
     const int padded = (count + 3) & ~3;   // staged as zeros beyond count and never offered
-    __syncthreads();
-    for (int f = (int)threadIdx.x; f < 3 * padded; f += kThreads) {
-      const int j = f / 3, c = f - 3 * j;
-      const float v = j < count ? yb[3 * (size_t)t0 + f] : 0.0f;
-      float *plane = c == 0 ? sx : (c == 1 ? sy : sz);
-      plane[j] = v;
-    }
-    __syncthreads();
+    stage_points(yb + 3 * (size_t)t0, count, padded, 0.0f, sx, sy, sz);
     for (int j = 0; j < padded; j += 4) {
-      const float4 tx = *reinterpret_cast<const float4 *>(&sx[j]);
-      const float4 ty = *reinterpret_cast<const float4 *>(&sy[j]);
-      const float4 tz = *reinterpret_cast<const float4 *>(&sz[j]);
-      const float ax[4] = {tx.x, tx.y, tx.z, tx.w};
-      const float ay[4] = {ty.x, ty.y, ty.z, ty.w};
-      const float az[4] = {tz.x, tz.y, tz.z, tz.w};
+      float ax[4], ay[4], az[4];
+      read_targets(sx, sy, sz, j, ax, ay, az);
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         if (j + k < count) {   // (the same on every thread)
@@ -1009,7 +1018,7 @@ __global__ __launch_bounds__(kThreads) void k_knn_merge(const unsigned long long
 // [B, N, K] of N queries: the sum of 2 g_e (p - o_e) over the row's entries e.  kTargets false: p is the queries'
 // cloud (Np == N), row p's entries are its own K slots and o_e = y[idx_e].  kTargets true: p is the targets' cloud,
 // the entries are order[offsets[p] .. offsets[p + 1]) of the inverted index (order [B, N K], offsets [B, Np + 1]) and
-// o_e = x[e / K].  Eight lanes per row.  grid (ceil(Np / kPointsPerBlock), B)
+// o_e = x[e / K].  grid (ceil(Np / kPointsPerBlock), B)
 template <bool kTargets>
 __global__ __launch_bounds__(kThreads) void k_knn_backward(
     const V3 *__restrict__ p_points, const V3 *__restrict__ o_points, const int32_t *__restrict__ p_lengths,
@@ -1017,15 +1026,12 @@ __global__ __launch_bounds__(kThreads) void k_knn_backward(
     const int32_t *__restrict__ idx, const int32_t *__restrict__ order, const int32_t *__restrict__ offsets,
     const float *__restrict__ grad, V3 *__restrict__ dp) {
   const int b = (int)blockIdx.y;
-  const int p = (int)blockIdx.x * kPointsPerBlock + (int)threadIdx.x / kLanesPerPoint;
-  const int sub = (int)threadIdx.x % kLanesPerPoint;
-  const bool have = p < Np;   // (whole groups of eight: the butterfly below stays inside one)
   const int pv = valid_count(p_lengths, b, Np), ov = valid_count(o_lengths, b, No);
   const int entries = N * K;   // (below 2^31: mr_knn_*'s limits)
   const size_t base = (size_t)b * entries;
   const V3 *ob = o_points + (size_t)b * No;
-  float dx = 0.0f, dy = 0.0f, dz = 0.0f;
-  if (have && p < pv) {
+  gather_rows(b, Np, dp, [&](int p, int sub, float &dx, float &dy, float &dz) {
+    if (p >= pv) return;
     const V3 me = p_points[(size_t)b * Np + p];
     int e0 = p * K, e1 = e0 + K;
     if constexpr (kTargets) {
@@ -1049,15 +1055,59 @@ __global__ __launch_bounds__(kThreads) void k_knn_backward(
       dy += g2 * (me.y - o.y);
       dz += g2 * (me.z - o.z);
     }
-  }
-  dx = group_sum(dx), dy = group_sum(dy), dz = group_sum(dz);
-  if (have && sub == 0) dp[(size_t)b * Np + p] = V3{dx, dy, dz};
+  });
 }
 
+// ---- launches ---------------------------------------------------------------------------------------------------
+// One kernel, workgroups of kThreads, on stream s -> MR_OK or MR_ELAUNCH.
+template <typename Kernel, typename... Args>
+int launch(Kernel kernel, dim3 grid, hipStream_t s, Args... args) {
+  hipLaunchKernelGGL(kernel, grid, dim3(kThreads), 0, s, args...);
+  return check_launch();
+}
+
+// rows of the last pass over the queries (the one that writes the distances): what k_nearest_mean adds per image
+inline unsigned partial_rows_of(const Plan &p, int N) {
+  return p.splits > 1 ? row_blocks_of(N) : (unsigned)p.query_blocks;
+}
+inline Layout nearest_layout(const Plan &p, int B, int N) {
+  return layout_of(p, B, 0, (size_t)N, partial_rows_of(p, N));
+}
+
+// the splits' K keys per query; nothing without a split
+inline Layout knn_layout(const Plan &p, int B, int N, int K) { return layout_of(p, B, 0, (size_t)N * K, 0); }
+
 inline Plan tri_plan_of(int B, int N, int T) { return plan_of(B, N, T, kTriTile, kTriWideQueries); }
-inline size_t tri_records_bytes(int B, int T) { return align_up((size_t)B * T * kRecWords * sizeof(float4), 256); }
 // triangle to point: the T triangles are the queries, one a lane, and the N points the targets that are split
 inline Plan point_plan_of(int B, int N, int T) { return plan_of(B, T, N, kPointTile, 1); }
+// both triangle searches, over `rows` queries (the points, or the triangles): the finish pass writes the partial sums
+inline Layout tri_layout(const Plan &p, int B, int rows, int T) {
+  return layout_of(p, B, align_up((size_t)B * T * kRecWords * sizeof(float4), 256), (size_t)rows, row_blocks_of(rows));
+}
+
+// What follows either triangle search: the lowest key of a row's splits -> its face / point, -1 without one
+// (k_nearest_merge: every row is a query, the other side's lengths bound the index), the chosen pair once more
+// (k_nt_finish) and the mean of the rows' distances: over the image's valid points, or with triangle rows over
+// its usable triangles (0 without one or without a valid point).
+template <bool kRowsAreTriangles>
+int finish_triangle_search(const Plan &p, const Workspace &w, const float *points, const int32_t *lengths,
+                           const int32_t *usable, int B, int N, int T, float *sqdist, int32_t *chosen, float *bary,
+                           float *total, hipStream_t s) {
+  const int R = kRowsAreTriangles ? T : N, O = kRowsAreTriangles ? N : T;
+  const int32_t *row_lengths = kRowsAreTriangles ? nullptr : lengths;
+  const int32_t *other_lengths = kRowsAreTriangles ? lengths : nullptr;
+  int rc = MR_OK;
+  if (w.keys)
+    rc = launch(k_nearest_merge, rows_grid(R, B), s, w.keys, p.splits, row_lengths, other_lengths, R, O, nullptr,
+                chosen, nullptr);
+  if (rc == MR_OK)
+    rc = launch(k_nt_finish<kRowsAreTriangles>, rows_grid(R, B), s, (const V3 *)points, w.records, lengths, N, T,
+                sqdist, chosen, (V3 *)bary, w.partials);
+  if (rc == MR_OK && total)
+    rc = launch(k_nearest_mean, dim3((unsigned)B), s, w.partials, (int)row_blocks_of(R),
+                kRowsAreTriangles ? usable : lengths, other_lengths, R, O, 1.0f, 0, total);
+  return rc;
+}
 
 }  // namespace
 
@@ -1069,38 +1119,22 @@ void nearest_plan(int B, int N, int M, int *splits, int *queries_per_lane, int *
   *workgroup = kThreads;
 }
 
-size_t nearest_ws(int B, int N, int M) {
-  const Plan p = plan_of(B, N, M);
-  return keys_bytes(p, B, N) + align_up((size_t)B * partial_rows_of(p, N) * sizeof(float), 256);
-}
+size_t nearest_ws(int B, int N, int M) { return nearest_layout(plan_of(B, N, M), B, N).bytes; }
 
 int launch_nearest_forward(const float *x, const float *y, const int32_t *x_lengths, const int32_t *y_lengths, int B,
                            int N, int M, float *sqdist, int32_t *idx, float *total, float weight, int accumulate,
                            void *ws, hipStream_t s) {
   const Plan p = plan_of(B, N, M);
-  unsigned long long *keys = p.splits > 1 ? (unsigned long long *)ws : nullptr;
-  float *partials = total ? (float *)((char *)ws + keys_bytes(p, B, N)) : nullptr;
-  const dim3 grid((unsigned)p.query_blocks, (unsigned)p.splits, (unsigned)B);
-  float *direct = keys ? nullptr : partials;
-  if (p.queries_per_lane == kWideQueries)
-    hipLaunchKernelGGL(k_nearest<kWideQueries>, grid, dim3(kThreads), 0, s, x, y, x_lengths, y_lengths, N, M, p.chunk,
-                       sqdist, idx, keys, direct);
-  else
-    hipLaunchKernelGGL(k_nearest<1>, grid, dim3(kThreads), 0, s, x, y, x_lengths, y_lengths, N, M, p.chunk, sqdist,
-                       idx, keys, direct);
-  int rc = check_launch();
-  if (rc != MR_OK) return rc;
-  if (keys) {
-    hipLaunchKernelGGL(k_nearest_merge, dim3(merge_blocks_of(N), (unsigned)B), dim3(kThreads), 0, s,
-                       (const unsigned long long *)keys, p.splits, x_lengths, y_lengths, N, M, sqdist, idx, partials);
-    rc = check_launch();
-    if (rc != MR_OK) return rc;
-  }
-  if (total) {
-    hipLaunchKernelGGL(k_nearest_mean, dim3((unsigned)B), dim3(kThreads), 0, s, (const float *)partials,
-                       (int)partial_rows_of(p, N), x_lengths, y_lengths, N, M, weight, accumulate, total);
-    rc = check_launch();
-  }
+  const Workspace w = carve(ws, p, nearest_layout(p, B, N), total != nullptr);
+  const auto search = p.queries_per_lane == kWideQueries ? k_nearest<kWideQueries> : k_nearest<1>;
+  int rc = launch(search, search_grid(p, B), s, x, y, x_lengths, y_lengths, N, M, p.chunk, sqdist, idx, w.keys,
+                  w.keys ? nullptr : w.partials);
+  if (rc == MR_OK && w.keys)
+    rc = launch(k_nearest_merge, rows_grid(N, B), s, w.keys, p.splits, x_lengths, y_lengths, N, M, sqdist, idx,
+                w.partials);
+  if (rc == MR_OK && total)
+    rc = launch(k_nearest_mean, dim3((unsigned)B), s, w.partials, (int)partial_rows_of(p, N), x_lengths, y_lengths, N,
+                M, weight, accumulate, total);
   return rc;
 }
 
@@ -1109,22 +1143,14 @@ int launch_nearest_backward(const float *x, const float *y, const int32_t *x_len
                             const int32_t *idx_yx, const int32_t *order_yx, const int32_t *offsets_yx,
                             const float *grad_points, const float *grad_images, float x_weight, float y_weight,
                             float *dx, float *dy, hipStream_t s) {
-  if (dx) {   // the gather half of x -> y and the scatter half of y -> x
-    const dim3 grid((unsigned)((N + kPointsPerBlock - 1) / kPointsPerBlock), (unsigned)B);
-    hipLaunchKernelGGL(k_nearest_backward, grid, dim3(kThreads), 0, s, (const V3 *)x, (const V3 *)y, x_lengths,
-                       y_lengths, N, M, idx_xy, grad_points, x_weight, order_yx, offsets_yx, (const float *)nullptr,
-                       y_weight, grad_images, (V3 *)dx);
-    const int rc = check_launch();
-    if (rc != MR_OK) return rc;
-  }
-  if (dy) {   // the gather half of y -> x and the scatter half of x -> y
-    const dim3 grid((unsigned)((M + kPointsPerBlock - 1) / kPointsPerBlock), (unsigned)B);
-    hipLaunchKernelGGL(k_nearest_backward, grid, dim3(kThreads), 0, s, (const V3 *)y, (const V3 *)x, y_lengths,
-                       x_lengths, M, N, idx_yx, (const float *)nullptr, y_weight, order_xy, offsets_xy, grad_points,
-                       x_weight, grad_images, (V3 *)dy);
-    return check_launch();
-  }
-  return MR_OK;
+  int rc = MR_OK;
+  if (dx)   // the gather half of x -> y and the scatter half of y -> x
+    rc = launch(k_nearest_backward, groups_grid(N, B), s, (const V3 *)x, (const V3 *)y, x_lengths, y_lengths, N, M,
+                idx_xy, grad_points, x_weight, order_yx, offsets_yx, nullptr, y_weight, grad_images, (V3 *)dx);
+  if (rc == MR_OK && dy)   // the gather half of y -> x and the scatter half of x -> y
+    rc = launch(k_nearest_backward, groups_grid(M, B), s, (const V3 *)y, (const V3 *)x, y_lengths, x_lengths, M, N,
+                idx_yx, nullptr, y_weight, order_xy, offsets_xy, grad_points, x_weight, grad_images, (V3 *)dy);
+  return rc;
 }
 
 void nearest_triangle_plan(int B, int N, int T, int *splits, int *queries_per_lane, int *triangle_tile,
@@ -1136,49 +1162,19 @@ void nearest_triangle_plan(int B, int N, int T, int *splits, int *queries_per_la
   *workgroup = kThreads;
 }
 
-// records | keys (splits > 1) | the finish pass's partial sums
-size_t nearest_triangle_ws(int B, int N, int T) {
-  const Plan p = tri_plan_of(B, N, T);
-  return tri_records_bytes(B, T) + keys_bytes(p, B, N) + align_up((size_t)B * merge_blocks_of(N) * sizeof(float), 256);
-}
+size_t nearest_triangle_ws(int B, int N, int T) { return tri_layout(tri_plan_of(B, N, T), B, N, T).bytes; }
 
 int launch_nearest_triangle_forward(const float *points, const float *vertices, const int32_t *triangles,
                                     const int32_t *lengths, int B, int N, int V, int T, float *sqdist, int32_t *face,
                                     float *bary, float *total, void *ws, hipStream_t s) {
   const Plan p = tri_plan_of(B, N, T);
-  float4 *records = (float4 *)ws;
-  unsigned long long *keys = p.splits > 1 ? (unsigned long long *)((char *)ws + tri_records_bytes(B, T)) : nullptr;
-  float *partials = total ? (float *)((char *)ws + tri_records_bytes(B, T) + keys_bytes(p, B, N)) : nullptr;
-  hipLaunchKernelGGL(k_nt_setup, dim3((unsigned)((T + kThreads - 1) / kThreads), (unsigned)B), dim3(kThreads), 0, s,
-                     (const V3 *)vertices, triangles, V, T, records);
-  int rc = check_launch();
+  const Workspace w = carve(ws, p, tri_layout(p, B, N, T), total != nullptr);
+  int rc = launch(k_nt_setup, rows_grid(T, B), s, (const V3 *)vertices, triangles, V, T, w.records);
   if (rc != MR_OK) return rc;
-  const dim3 grid((unsigned)p.query_blocks, (unsigned)p.splits, (unsigned)B);
-  if (p.queries_per_lane == kTriWideQueries)
-    hipLaunchKernelGGL(k_nt_search<F2>, grid, dim3(kThreads), 0, s, points, (const float4 *)records, lengths, N, T,
-                       p.chunk, face, keys);
-  else
-    hipLaunchKernelGGL(k_nt_search<float>, grid, dim3(kThreads), 0, s, points, (const float4 *)records, lengths, N, T,
-                       p.chunk, face, keys);
-  rc = check_launch();
+  const auto search = p.queries_per_lane == kTriWideQueries ? k_nt_search<F2> : k_nt_search<float>;
+  rc = launch(search, search_grid(p, B), s, points, w.records, lengths, N, T, p.chunk, face, w.keys);
   if (rc != MR_OK) return rc;
-  const dim3 rows(merge_blocks_of(N), (unsigned)B);
-  if (keys) {   // the lowest key of a query's splits -> its face, -1 without one
-    hipLaunchKernelGGL(k_nearest_merge, rows, dim3(kThreads), 0, s, (const unsigned long long *)keys, p.splits, lengths,
-                       (const int32_t *)nullptr, N, T, (float *)nullptr, face, (float *)nullptr);
-    rc = check_launch();
-    if (rc != MR_OK) return rc;
-  }
-  hipLaunchKernelGGL(k_nt_finish, rows, dim3(kThreads), 0, s, (const V3 *)points, (const float4 *)records, lengths, N, T,
-                     sqdist, face, (V3 *)bary, partials);
-  rc = check_launch();
-  if (rc != MR_OK) return rc;
-  if (total) {
-    hipLaunchKernelGGL(k_nearest_mean, dim3((unsigned)B), dim3(kThreads), 0, s, (const float *)partials,
-                       (int)merge_blocks_of(N), lengths, (const int32_t *)nullptr, N, T, 1.0f, 0, total);
-    rc = check_launch();
-  }
-  return rc;
+  return finish_triangle_search<false>(p, w, points, lengths, nullptr, B, N, T, sqdist, face, bary, total, s);
 }
 
 int launch_nearest_triangle_backward(const float *points, const float *vertices, const int32_t *triangles,
@@ -1186,21 +1182,15 @@ int launch_nearest_triangle_backward(const float *points, const float *vertices,
                                      const float *bary, const int32_t *order, const int32_t *offsets,
                                      const float *grad_points, const float *grad_images, float *dpoints,
                                      float *dvertices, hipStream_t s) {
-  if (dpoints) {
-    hipLaunchKernelGGL(k_nt_backward_points, dim3(merge_blocks_of(N), (unsigned)B), dim3(kThreads), 0, s,
-                       (const V3 *)points, (const V3 *)vertices, triangles, lengths, N, V, T, face, (const V3 *)bary,
-                       grad_points, grad_images, (V3 *)dpoints);
-    const int rc = check_launch();
-    if (rc != MR_OK) return rc;
-  }
-  if (dvertices) {
-    const dim3 grid((unsigned)((V + kPointsPerBlock - 1) / kPointsPerBlock), (unsigned)B);
-    hipLaunchKernelGGL(k_nt_backward_vertices<false>, grid, dim3(kThreads), 0, s, (const V3 *)points,
-                       (const V3 *)vertices, triangles, lengths, N, V, T, face, (const V3 *)bary, order, offsets,
-                       grad_points, grad_images, (const int32_t *)nullptr, (V3 *)dvertices);
-    return check_launch();
-  }
-  return MR_OK;
+  int rc = MR_OK;
+  if (dpoints)
+    rc = launch(k_nt_backward_points, rows_grid(N, B), s, (const V3 *)points, (const V3 *)vertices, triangles, lengths,
+                N, V, T, face, (const V3 *)bary, grad_points, grad_images, (V3 *)dpoints);
+  if (rc == MR_OK && dvertices)
+    rc = launch(k_nt_backward_vertices<false>, groups_grid(V, B), s, (const V3 *)points, (const V3 *)vertices,
+                triangles, lengths, N, V, T, face, (const V3 *)bary, order, offsets, grad_points, grad_images, nullptr,
+                (V3 *)dvertices);
+  return rc;
 }
 
 void nearest_point_of_triangle_plan(int B, int N, int T, int *splits, int *points_per_step, int *point_tile,
@@ -1211,54 +1201,21 @@ void nearest_point_of_triangle_plan(int B, int N, int T, int *splits, int *point
   *workgroup = kThreads;
 }
 
-// records | keys (splits > 1) | the finish pass's partial sums
-size_t nearest_point_of_triangle_ws(int B, int N, int T) {
-  const Plan p = point_plan_of(B, N, T);
-  return tri_records_bytes(B, T) + keys_bytes(p, B, T) + align_up((size_t)B * merge_blocks_of(T) * sizeof(float), 256);
-}
+size_t nearest_point_of_triangle_ws(int B, int N, int T) { return tri_layout(point_plan_of(B, N, T), B, T, T).bytes; }
 
 int launch_nearest_point_of_triangle_forward(const float *points, const float *vertices, const int32_t *triangles,
                                              const int32_t *lengths, int B, int N, int V, int T, float *sqdist,
                                              int32_t *index, float *bary, float *total, int32_t *usable, void *ws,
                                              hipStream_t s) {
   const Plan p = point_plan_of(B, N, T);
-  float4 *records = (float4 *)ws;
-  unsigned long long *keys = p.splits > 1 ? (unsigned long long *)((char *)ws + tri_records_bytes(B, T)) : nullptr;
-  float *partials = total ? (float *)((char *)ws + tri_records_bytes(B, T) + keys_bytes(p, B, T)) : nullptr;
-  const dim3 rows(merge_blocks_of(T), (unsigned)B);
-  hipLaunchKernelGGL(k_nt_setup, rows, dim3(kThreads), 0, s, (const V3 *)vertices, triangles, V, T, records);
-  int rc = check_launch();
+  const Workspace w = carve(ws, p, tri_layout(p, B, T, T), total != nullptr);
+  int rc = launch(k_nt_setup, rows_grid(T, B), s, (const V3 *)vertices, triangles, V, T, w.records);
   if (rc != MR_OK) return rc;
-  const dim3 grid((unsigned)p.query_blocks, (unsigned)p.splits, (unsigned)B);
-  if (N >= kPackedFrom)
-    hipLaunchKernelGGL(k_tp_search<F2>, grid, dim3(kThreads), 0, s, points, (const float4 *)records, lengths, N, T,
-                       p.chunk, index, keys);
-  else
-    hipLaunchKernelGGL(k_tp_search<float>, grid, dim3(kThreads), 0, s, points, (const float4 *)records, lengths, N, T,
-                       p.chunk, index, keys);
-  rc = check_launch();
+  const auto search = N >= kPackedFrom ? k_tp_search<F2> : k_tp_search<float>;
+  rc = launch(search, search_grid(p, B), s, points, w.records, lengths, N, T, p.chunk, index, w.keys);
+  if (rc == MR_OK && usable) rc = launch(k_tp_usable, dim3(1), s, triangles, V, T, B, usable);   // the mean's divisor
   if (rc != MR_OK) return rc;
-  if (keys) {   // the lowest key of a triangle's splits -> its point, -1 without one: every triangle row is a query
-    hipLaunchKernelGGL(k_nearest_merge, rows, dim3(kThreads), 0, s, (const unsigned long long *)keys, p.splits,
-                       (const int32_t *)nullptr, lengths, T, N, (float *)nullptr, index, (float *)nullptr);
-    rc = check_launch();
-    if (rc != MR_OK) return rc;
-  }
-  hipLaunchKernelGGL(k_tp_finish, rows, dim3(kThreads), 0, s, (const V3 *)points, (const float4 *)records, lengths, N,
-                     T, sqdist, index, (V3 *)bary, partials);
-  rc = check_launch();
-  if (rc != MR_OK) return rc;
-  if (usable) {
-    hipLaunchKernelGGL(k_tp_usable, dim3(1), dim3(kThreads), 0, s, triangles, V, T, B, usable);
-    rc = check_launch();
-    if (rc != MR_OK) return rc;
-  }
-  if (total) {   // the mean over the usable triangles; 0 without one or without a valid point
-    hipLaunchKernelGGL(k_nearest_mean, dim3((unsigned)B), dim3(kThreads), 0, s, (const float *)partials,
-                       (int)merge_blocks_of(T), (const int32_t *)usable, lengths, T, N, 1.0f, 0, total);
-    rc = check_launch();
-  }
-  return rc;
+  return finish_triangle_search<true>(p, w, points, lengths, usable, B, N, T, sqdist, index, bary, total, s);
 }
 
 int launch_nearest_point_of_triangle_backward(const float *points, const float *vertices, const int32_t *triangles,
@@ -1268,22 +1225,16 @@ int launch_nearest_point_of_triangle_backward(const float *points, const float *
                                               const int32_t *point_offsets, const float *grad_triangles,
                                               const float *grad_images, const int32_t *usable, float *dpoints,
                                               float *dvertices, hipStream_t s) {
-  if (dpoints) {
-    const dim3 grid((unsigned)((N + kPointsPerBlock - 1) / kPointsPerBlock), (unsigned)B);
-    hipLaunchKernelGGL(k_tp_backward_points, grid, dim3(kThreads), 0, s, (const V3 *)points, (const V3 *)vertices,
-                       triangles, lengths, N, V, T, index, (const V3 *)bary, point_order, point_offsets, grad_triangles,
-                       grad_images, usable, (V3 *)dpoints);
-    const int rc = check_launch();
-    if (rc != MR_OK) return rc;
-  }
-  if (dvertices) {
-    const dim3 grid((unsigned)((V + kPointsPerBlock - 1) / kPointsPerBlock), (unsigned)B);
-    hipLaunchKernelGGL(k_nt_backward_vertices<true>, grid, dim3(kThreads), 0, s, (const V3 *)points,
-                       (const V3 *)vertices, triangles, lengths, N, V, T, index, (const V3 *)bary, corner_order,
-                       corner_offsets, grad_triangles, grad_images, usable, (V3 *)dvertices);
-    return check_launch();
-  }
-  return MR_OK;
+  int rc = MR_OK;
+  if (dpoints)
+    rc = launch(k_tp_backward_points, groups_grid(N, B), s, (const V3 *)points, (const V3 *)vertices, triangles,
+                lengths, N, V, T, index, (const V3 *)bary, point_order, point_offsets, grad_triangles, grad_images,
+                usable, (V3 *)dpoints);
+  if (rc == MR_OK && dvertices)
+    rc = launch(k_nt_backward_vertices<true>, groups_grid(V, B), s, (const V3 *)points, (const V3 *)vertices, triangles,
+                lengths, N, V, T, index, (const V3 *)bary, corner_order, corner_offsets, grad_triangles, grad_images,
+                usable, (V3 *)dvertices);
+  return rc;
 }
 
 int knn_max_k() { return kKnnMaxK; }
@@ -1298,8 +1249,7 @@ void knn_plan(int B, int N, int M, int K, int *splits, int *queries_per_lane, in
   *workgroup = kThreads;
 }
 
-// the splits' keys; nothing without a split
-size_t knn_ws(int B, int N, int M, int K) { return knn_keys_bytes(knn_plan_of(B, N, M, K), B, N, K); }
+size_t knn_ws(int B, int N, int M, int K) { return knn_layout(knn_plan_of(B, N, M, K), B, N, K).bytes; }
 
 namespace {
 
@@ -1307,19 +1257,12 @@ template <int C>
 int launch_knn_of(const Plan &p, const float *x, const float *y, const int32_t *x_lengths, const int32_t *y_lengths,
                   int B, int N, int M, int K, float *sqdist, int32_t *idx, void *ws, hipStream_t s) {
   constexpr int kWide = knn_wide_queries(C);
-  unsigned long long *keys = p.splits > 1 ? (unsigned long long *)ws : nullptr;
-  const dim3 grid((unsigned)p.query_blocks, (unsigned)p.splits, (unsigned)B);
-  if (kWide > 1 && p.queries_per_lane == kWide)
-    hipLaunchKernelGGL((k_knn<C, kWide>), grid, dim3(kThreads), 0, s, x, y, x_lengths, y_lengths, N, M, K, p.chunk,
-                       sqdist, idx, keys);
-  else
-    hipLaunchKernelGGL((k_knn<C, 1>), grid, dim3(kThreads), 0, s, x, y, x_lengths, y_lengths, N, M, K, p.chunk, sqdist,
-                       idx, keys);
-  int rc = check_launch();
-  if (rc != MR_OK || !keys) return rc;
-  hipLaunchKernelGGL(k_knn_merge<C>, dim3(merge_blocks_of(N), (unsigned)B), dim3(kThreads), 0, s,
-                     (const unsigned long long *)keys, p.splits, x_lengths, y_lengths, N, M, K, sqdist, idx);
-  return check_launch();
+  unsigned long long *keys = carve(ws, p, knn_layout(p, B, N, K), false).keys;
+  const auto search = (kWide > 1 && p.queries_per_lane == kWide) ? k_knn<C, kWide> : k_knn<C, 1>;
+  int rc = launch(search, search_grid(p, B), s, x, y, x_lengths, y_lengths, N, M, K, p.chunk, sqdist, idx, keys);
+  if (rc == MR_OK && keys)
+    rc = launch(k_knn_merge<C>, rows_grid(N, B), s, keys, p.splits, x_lengths, y_lengths, N, M, K, sqdist, idx);
+  return rc;
 }
 
 }  // namespace
@@ -1338,21 +1281,14 @@ int launch_knn_forward(const float *x, const float *y, const int32_t *x_lengths,
 int launch_knn_backward(const float *x, const float *y, const int32_t *x_lengths, const int32_t *y_lengths, int B, int N,
                         int M, int K, const float *sqdist, const int32_t *idx, const int32_t *order,
                         const int32_t *offsets, const float *grad, float *dx, float *dy, hipStream_t s) {
-  if (dx) {
-    const dim3 grid((unsigned)((N + kPointsPerBlock - 1) / kPointsPerBlock), (unsigned)B);
-    hipLaunchKernelGGL(k_knn_backward<false>, grid, dim3(kThreads), 0, s, (const V3 *)x, (const V3 *)y, x_lengths,
-                       y_lengths, N, M, N, K, sqdist, idx, (const int32_t *)nullptr, (const int32_t *)nullptr, grad,
-                       (V3 *)dx);
-    const int rc = check_launch();
-    if (rc != MR_OK) return rc;
-  }
-  if (dy) {
-    const dim3 grid((unsigned)((M + kPointsPerBlock - 1) / kPointsPerBlock), (unsigned)B);
-    hipLaunchKernelGGL(k_knn_backward<true>, grid, dim3(kThreads), 0, s, (const V3 *)y, (const V3 *)x, y_lengths,
-                       x_lengths, M, N, N, K, sqdist, idx, order, offsets, grad, (V3 *)dy);
-    return check_launch();
-  }
-  return MR_OK;
+  int rc = MR_OK;
+  if (dx)
+    rc = launch(k_knn_backward<false>, groups_grid(N, B), s, (const V3 *)x, (const V3 *)y, x_lengths, y_lengths, N, M,
+                N, K, sqdist, idx, nullptr, nullptr, grad, (V3 *)dx);
+  if (rc == MR_OK && dy)
+    rc = launch(k_knn_backward<true>, groups_grid(M, B), s, (const V3 *)y, (const V3 *)x, y_lengths, x_lengths, M, N, N,
+                K, sqdist, idx, order, offsets, grad, (V3 *)dy);
+  return rc;
 }
 
 }  // namespace mr
