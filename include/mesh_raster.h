@@ -840,6 +840,34 @@ int mr_knn_backward(const float *x, const float *y, const int32_t *x_lengths, co
                     int M, int K, const float *sqdist, const int32_t *idx, const int32_t *order, const int32_t *offsets,
                     const float *grad, float *dx, float *dy, void *stream);
 
+/* ---- farthest-point sampling of point clouds (no reference counterpart) ----
+ * Per cloud b with length_b = lengths[b] (N without lengths), K indices chosen greedily (INTEGRATION.md,
+ * "Farthest-point sampling").  The definition is part of the interface:
+ *   idx[b,0] = start_idx[b] clamped to [0, length_b) (0 without start_idx);
+ *   every valid point carries a float32 running distance m_i: +inf, or 0 for a point with a non-finite coordinate,
+ *   which is never updated;
+ *   after the selection of s:  d_i = fl(fl(fl(dx dx) + fl(dy dy)) + fl(dz dz)),  dx = fl(x_i - x_s), in un-fused
+ *   binary32 in exactly this order;  m_i <- d_i if d_i < m_i (a NaN d_i changes nothing);  m_s <- -1;
+ *   the next selection is the point with the largest m_i, the lowest index among equals.
+ * The indices of a cloud are pairwise distinct whenever K <= length_b (a duplicate of a selected point has m = 0 > -1).
+ *   points [B,N,3] f32;  lengths, start_idx [B] i32 (device) or NULL, clamped by the kernels
+ *   idx [B,K] i32 out;  radius [B,K] f32 out: m of the selected point at the moment of its selection, +inf in slot 0,
+ *   non-increasing from slot 1.  Slots k >= length_b get idx -1, radius 0.  Padded coordinates influence nothing.
+ * Two routes with bit-identical results.  Route 1: one launch, one workgroup of `workgroup_size` lanes per cloud that
+ * keeps `points_per_lane` points a lane in registers for all K steps (N <= 24576).  Route 2: one launch per step over
+ * `slices` workgroups per cloud, the running distances in the workspace, K + 1 launches; stream order is the only
+ * synchronisation between workgroups.  mr_farthest_plan: the route and launch shape the library takes (route 0 of
+ * mr_farthest_forward), a pure host function; it depends on N alone.  route 1 / 2 force one; a forced route 1 whose
+ * N it cannot hold is MR_EINVAL.  The workspace (B * N * 4 bytes rounded up to 256, plus 2 * B * slices * 32 for the
+ * partial results; needed by every call) serves either route.  All entry points only enqueue on `stream`: capturable
+ * in a HIP graph, nothing is read back.
+ * 1 <= B <= 65535, 1 <= N < 2^28, 1 <= K < 2^24, B * K < 2^31; anything else is MR_EINVAL (queries return 0) before a
+ * device is touched. */
+int mr_farthest_plan(int B, int N, int K, int *route, int *workgroup_size, int *points_per_lane, int *slices);
+size_t mr_farthest_workspace_bytes(int B, int N, int K);
+int mr_farthest_forward(const float *points, const int32_t *lengths, const int32_t *start_idx, int B, int N, int K,
+                        int route, int32_t *idx, float *radius, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- point to nearest triangle: the point-to-mesh distance (no reference counterpart) ----
  * Per image b, for every query p_i with i < lengths[b], over the T triangles of one shared topology
  * ("Point-cloud losses"):

@@ -51,6 +51,12 @@ int mr_debug_set_lanes_rows(int rows);
 /* Strip height the most recent k_accumulate_lanes launch of any thread of this process used (0 before the first). */
 int mr_debug_last_lanes_rows(void);
 
+/* Launch shape of farthest-point sampling's route A (mr_farthest_forward: one workgroup per cloud) for the calling
+ * thread's next launches: workgroup_size 64 / 256 / 1024 with points_per_lane 4 / 8 / 16 / 20 / 24; (0, 0) = the plan's
+ * (default); anything else: MR_EINVAL.  A shape that cannot hold N makes a forced route A, and a call the plan gives
+ * to route A, return MR_EINVAL.  tools/fps_bench.py times the shapes with it; results are bit-identical in all. */
+int mr_debug_set_farthest_shape(int workgroup_size, int points_per_lane);
+
 /* Stage-timing probes of k_raster.  Only a library built with -DMR_PROBES (make probes ->
  * libmesh_raster_hip_probes.so) contains the probe instantiations; the production library
  * returns MR_EINVAL for every value but 0, its kernel has no probe code at all.

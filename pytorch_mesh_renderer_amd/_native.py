@@ -405,6 +405,18 @@ def lib():
         except AttributeError as e:   # the K-nearest-neighbour entry points came without an ABI version bump
             raise NativeLibraryError("%s lacks the K-nearest-neighbour entry points (%s): rebuild it (make -C "
                                      "pytorch_mesh_renderer_amd/csrc)" % (LIB_PATH, e))
+        try:
+            L.mr_farthest_plan.argtypes = [ci] * 3 + [vp] * 4
+            L.mr_farthest_plan.restype = ci
+            L.mr_farthest_workspace_bytes.argtypes = [ci] * 3
+            L.mr_farthest_workspace_bytes.restype = sz
+            L.mr_farthest_forward.argtypes = [vp] * 3 + [ci] * 4 + [vp, vp, vp, sz, vp]
+            L.mr_farthest_forward.restype = ci
+            L.mr_debug_set_farthest_shape.argtypes = [ci, ci]
+            L.mr_debug_set_farthest_shape.restype = ci
+        except AttributeError as e:   # the farthest-point entry points came without an ABI version bump
+            raise NativeLibraryError("%s lacks the farthest-point sampling entry points (%s): rebuild it (make -C "
+                                     "pytorch_mesh_renderer_amd/csrc)" % (LIB_PATH, e))
         _lib = L
     return _lib
 
@@ -1252,6 +1264,60 @@ def knn_backward(x, y, x_lengths, y_lengths, sqdist, idx, grad, index=None, want
                                _ptr(dy), _stream(dev))
     _check(rc, "mr_knn_backward")
     return dx, dy
+
+
+FARTHEST_ROUTE_PLAN, FARTHEST_ROUTE_RESIDENT, FARTHEST_ROUTE_STEPS = 0, 1, 2   # mr_farthest_forward's `route`
+_FARTHEST_TAKES = "1..65535 clouds of 1..2^28 - 1 points and 1..2^24 - 1 samples with B * K < 2^31"
+
+
+def farthest_plan(B, N, K):
+    """The route and launch shape mr_farthest_forward takes for B clouds of N points and K samples, a pure host
+    function: {"route" (1: one launch, the cloud in one workgroup's registers; 2: one launch per step),
+    "workgroup_size", "points_per_lane", "slices"} (include/mesh_raster.h)."""
+    return _plan("farthest_plan", (B, N, K), ("route", "workgroup_size", "points_per_lane", "slices"), _FARTHEST_TAKES)
+
+
+def debug_set_farthest_shape(workgroup_size, points_per_lane):
+    """Measurement and tests (include/mesh_raster_debug.h): route 1's launch shape for THIS thread's next calls;
+    (0, 0) = the plan's."""
+    _check(lib().mr_debug_set_farthest_shape(int(workgroup_size), int(points_per_lane)), "mr_debug_set_farthest_shape")
+
+
+def _chk_farthest(points, K, lengths, start_idx):
+    _chk("points", points, _F32, None, None, 3)
+    B, N, _ = points.shape
+    if not isinstance(K, int) or isinstance(K, bool) or not 1 <= K < 1 << 24:
+        raise ValueError("K must be an int in [1, 2^24), got %r" % (K,))
+    if not 1 <= B <= 65535 or not 1 <= N < 1 << 28 or B * K >= 1 << 31:
+        raise ValueError("farthest-point sampling takes %s, got %s with K = %d" % (_FARTHEST_TAKES, list(points.shape), K))
+    for name, t in (("lengths", lengths), ("start_idx", start_idx)):
+        if t is not None:
+            _chk(name, t, _I32, B)
+    return B, N
+
+
+def farthest_forward(points, K, lengths=None, start_idx=None, route=FARTHEST_ROUTE_PLAN):
+    """points [B,N,3] f32, lengths / start_idx [B] i32 or None (device) -> (idx [B,K] i32, radius [B,K] f32):
+    mr_farthest_forward.  route: FARTHEST_ROUTE_PLAN, or one of the two forced (a forced FARTHEST_ROUTE_RESIDENT
+    that cannot hold N is a ValueError)."""
+    B, N = _chk_farthest(points, K, lengths, start_idx)
+    if route not in (FARTHEST_ROUTE_PLAN, FARTHEST_ROUTE_RESIDENT, FARTHEST_ROUTE_STEPS):
+        raise ValueError("route must be 0 (the plan's), 1 or 2, got %r" % (route,))
+    dev = _require_device(points, *[t for t in (lengths, start_idx) if t is not None])
+    L = lib()
+    points = points.contiguous()
+    lengths = lengths.contiguous() if lengths is not None else None
+    start_idx = start_idx.contiguous() if start_idx is not None else None
+    idx = torch.empty(B, K, dtype=_I32, device=dev)
+    radius = torch.empty(B, K, dtype=_F32, device=dev)
+    with torch.cuda.device(dev):
+        ws, have = _workspace(dev, L.mr_farthest_workspace_bytes(B, N, K))
+        rc = L.mr_farthest_forward(_ptr(points), _ptr(lengths), _ptr(start_idx), B, N, K, int(route), _ptr(idx),
+                                   _ptr(radius), _ptr(ws), have, _stream(dev))
+    if rc == MR_EINVAL and route == FARTHEST_ROUTE_RESIDENT:
+        raise ValueError("the one-workgroup route of farthest-point sampling cannot hold %d points" % N)
+    _check(rc, "mr_farthest_forward")
+    return idx, radius
 
 
 def nearest_triangle_plan(B, N, T):

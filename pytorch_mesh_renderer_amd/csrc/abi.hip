@@ -90,6 +90,10 @@ int mr_debug_set_lanes_rows(int rows) {
 
 int mr_debug_last_lanes_rows(void) { return mr::g_last_lanes_rows; }
 
+int mr_debug_set_farthest_shape(int workgroup_size, int points_per_lane) {
+  return mr::farthest_set_shape(workgroup_size, points_per_lane);
+}
+
 int mr_debug_set_raster_probe(int probe) {
 #ifdef MR_PROBES
   static const int kProbes[] = {0, 1, 2, 3, 8, 16, 32, 40, 48, 64};
@@ -927,6 +931,33 @@ int mr_nearest_backward(const float *x, const float *y, const int32_t *x_lengths
   if (dy && idx_xy && !order_xy) return MR_EINVAL;
   return mr::launch_nearest_backward(x, y, x_lengths, y_lengths, B, N, M, idx_xy, order_xy, offsets_xy,
                                      idx_yx, order_yx, offsets_yx, grad_points, grad_images, x_weight, y_weight, dx, dy,
+                                     (hipStream_t)stream);
+}
+
+inline bool bad_farthest_dims(int B, int N, int K) {
+  return B < 1 || B > 65535 || N < 1 || N >= (1 << 28) || K < 1 || K >= (1 << 24) ||
+         (size_t)B * K >= ((size_t)1 << 31);
+}
+
+int mr_farthest_plan(int B, int N, int K, int *route, int *workgroup_size, int *points_per_lane, int *slices) {
+  if (bad_farthest_dims(B, N, K) || !route || !workgroup_size || !points_per_lane || !slices) return MR_EINVAL;
+  mr::farthest_plan(B, N, K, route, workgroup_size, points_per_lane, slices);
+  return MR_OK;
+}
+
+size_t mr_farthest_workspace_bytes(int B, int N, int K) {
+  if (bad_farthest_dims(B, N, K)) return 0;
+  return mr::farthest_ws(B, N, K);
+}
+
+int mr_farthest_forward(const float *points, const int32_t *lengths, const int32_t *start_idx, int B, int N, int K,
+                        int route, int32_t *idx, float *radius, void *workspace, size_t workspace_bytes,
+                        void *stream) {
+  if (bad_farthest_dims(B, N, K) || route < 0 || route > 2) return MR_EINVAL;
+  if (!points || !idx || !radius) return MR_EINVAL;
+  const int rc = check_ws(workspace, workspace_bytes, mr::farthest_ws(B, N, K));
+  if (rc != MR_OK) return rc;
+  return mr::launch_farthest_forward(points, lengths, start_idx, B, N, K, route, idx, radius, workspace,
                                      (hipStream_t)stream);
 }
 

@@ -285,6 +285,12 @@ int launch_knn_forward(const float *x, const float *y, const int32_t *x_lengths,
 int launch_knn_backward(const float *x, const float *y, const int32_t *x_lengths, const int32_t *y_lengths, int B, int N,
                         int M, int K, const float *sqdist, const int32_t *idx, const int32_t *order,
                         const int32_t *offsets, const float *grad, float *dx, float *dy, hipStream_t s);
+// farthest-point sampling, mr_farthest_* (farthest.hip)
+int farthest_set_shape(int workgroup, int points_per_lane);
+void farthest_plan(int B, int N, int K, int *route, int *workgroup, int *points_per_lane, int *slices);
+size_t farthest_ws(int B, int N, int K);
+int launch_farthest_forward(const float *points, const int32_t *lengths, const int32_t *start_idx, int B, int N, int K,
+                            int route, int32_t *idx, float *radius, void *ws, hipStream_t s);
 // point to nearest triangle, mr_nearest_triangle_* (nearest.hip)
 void nearest_triangle_plan(int B, int N, int T, int *splits, int *queries_per_lane, int *triangle_tile, int *workgroup);
 size_t nearest_triangle_ws(int B, int N, int T);

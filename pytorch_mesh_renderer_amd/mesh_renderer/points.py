@@ -12,7 +12,9 @@ file and the same split between the HIP and the torch path; triangle_nearest_poi
 other direction, every triangle against its nearest point, and point_mesh_face_distance is the sum of the two means.
 knn_points is the K-neighbour form of nearest_points (a sorted list of K keys per query in registers, same file, same
 split between the two paths), knn_gather reads values at its indices, and estimate_point_normals is its first
-consumer: the normals of a scan from the covariance of every point's neighbourhood.
+consumer: the normals of a scan from the covariance of every point's neighbourhood.  sample_farthest_points thins a
+cloud to K well-spread points before any of these O(N M) searches (csrc/farthest.hip on a HIP device, a torch loop
+of K steps elsewhere; both follow one bit-exact definition).
 """
 import torch
 from torch.autograd.function import once_differentiable
@@ -378,6 +380,91 @@ def estimate_point_normals(points, K=16, lengths=None, orient_to=None):
             flip = lead < 0
         normals = torch.where(flip, -normals, normals).to(points.dtype)
     return normals[0] if single else normals
+
+
+# ---- farthest-point sampling ------------------------------------------------------------------------------------------
+
+def _farthest_torch(points, K, lengths, start_idx):
+    """sample_farthest_points' indices and radii as a torch loop of K steps on the device and in the dtype of points
+    [B,N,3], without a graph: the definition, step by step.  -> (idx [B,K] int32, radius [B,K])."""
+    B, N, _ = points.shape
+    dev, dtype = points.device, points.dtype
+    with torch.no_grad():
+        p = points.detach()
+        n_valid = lengths.long() if lengths is not None else torch.full((B,), N, dtype=torch.int64, device=dev)
+        position = torch.arange(N, device=dev)[None, :]
+        valid = position < n_valid[:, None]
+        finite = torch.isfinite(p).all(dim=-1)
+        m = torch.where(finite, torch.full((B, N), float("inf"), dtype=dtype, device=dev),
+                        torch.zeros((), dtype=dtype, device=dev))
+        m = torch.where(valid, m, torch.full_like(m, -1.0))
+        s = start_idx.long() if start_idx is not None else torch.zeros(B, dtype=torch.int64, device=dev)
+        s = torch.minimum(s, n_valid - 1).clamp(min=0)
+        r = torch.full((B,), float("inf"), dtype=dtype, device=dev)
+        idx = torch.full((B, K), -1, dtype=torch.int64, device=dev)
+        radius = torch.zeros(B, K, dtype=dtype, device=dev)
+        for k in range(K):
+            live = n_valid > k
+            idx[:, k] = torch.where(live, s, torch.full_like(s, -1))
+            radius[:, k] = torch.where(live, r, torch.zeros_like(r))
+            if k + 1 == K:
+                break
+            diff = p - torch.gather(p, 1, s[:, None, None].expand(-1, 1, 3))
+            dx, dy, dz = diff[..., 0], diff[..., 1], diff[..., 2]
+            d = (dx * dx + dy * dy) + dz * dz
+            m = torch.where(d < m, d, m)                       # a NaN distance changes nothing
+            m.scatter_(1, s[:, None], -1.0)
+            r = m.max(dim=1).values
+            s = torch.where(m == r[:, None], position, torch.full_like(position, N)).min(dim=1).values   # the lowest
+            s = s.clamp(max=N - 1)
+    return idx.to(torch.int32), radius
+
+
+def sample_farthest_points(points, K, lengths=None, start_idx=None, return_radius=False):
+    """points [B,N,3] (or [N,3]: one cloud, results without the batch axis), K a Python int >= 1 -> (sampled [B,K,3],
+    idx [B,K] int32[, radius [B,K] with return_radius]): K points of every cloud chosen greedily, each the farthest
+    from those chosen before it.  The definition is part of the interface; length_b is lengths[b], or N:
+
+      idx[b,0] = start_idx[b] clamped to [0, length_b) (0 without start_idx).  Every valid point carries a running
+      distance m_i in the points' dtype, +inf at first.  After point s is selected, d_i = ((dx dx) + (dy dy)) + (dz dz)
+      with dx = x_i - x_s, every operation rounded on its own in exactly this order; m_i becomes d_i if d_i < m_i (a NaN
+      d_i changes nothing) and m_s becomes -1.  The next point is the one with the largest m_i, the lowest index among
+      equals.
+
+    The K indices of a cloud are pairwise distinct whenever K <= length_b (a duplicate of a selected point has
+    m = 0 > -1 and is taken before anything repeats).  A point with a non-finite coordinate has m_i = 0 from the start
+    and is never updated: it is selected only when nothing finite is farther than 0, and as a selected point it moves
+    nobody.  Slots k >= length_b (an empty cloud, K > length_b) get idx -1 and sampled 0; padded coordinates
+    influence nothing.  radius[b,k] is m of the selected point at the moment of its selection: +inf for slot 0,
+    non-increasing from slot 1, 0 for empty slots; radius[b,K-1] is the squared distance within which the first K - 1
+    samples cover the cloud.
+
+    sampled = points at idx, a torch gather: differentiable in points, and a slot with idx -1 passes no gradient;
+    the indices of a cloud are distinct, so the gradient is bitwise reproducible.  idx and radius are not
+    differentiable.  lengths, start_idx: optional integer [B] tensors on the clouds' device, clamped on the device
+    (nothing is read back).  On a HIP device with float32 clouds the selection is csrc/farthest.hip's (one launch that
+    keeps the cloud in one workgroup's registers, or one launch per step for large clouds; bit-identical);
+    otherwise a torch loop of K steps."""
+    _cloud("points", points)
+    if not isinstance(K, int) or isinstance(K, bool) or K < 1:
+        raise ValueError("K must be an int >= 1, got %r" % (K,))
+    single = points.dim() == 2
+    p = points.unsqueeze(0) if single else points
+    B, N, _ = p.shape
+    if B < 1:
+        raise ValueError("points must hold at least one cloud, got %s" % list(points.shape))
+    if single:
+        lengths = lengths.reshape(1) if torch.is_tensor(lengths) and lengths.dim() == 0 else lengths
+        start_idx = start_idx.reshape(1) if torch.is_tensor(start_idx) and start_idx.dim() == 0 else start_idx
+    lengths = _lengths("lengths", lengths, B, N, p)
+    start_idx = _lengths("start_idx", start_idx, B, N - 1, p)
+    if _on_hip_path(p):
+        idx, radius = _native.farthest_forward(p.detach().contiguous(), K, lengths, start_idx)
+    else:
+        idx, radius = _farthest_torch(p, K, lengths, start_idx)
+    sampled = knn_gather(p, idx[:, :, None])[:, :, 0]
+    out = (sampled, idx, radius) if return_radius else (sampled, idx)
+    return tuple(t[0] for t in out) if single else out
 
 
 def _mesh(vertices, triangles):
