@@ -868,6 +868,51 @@ size_t mr_farthest_workspace_bytes(int B, int N, int K);
 int mr_farthest_forward(const float *points, const int32_t *lengths, const int32_t *start_idx, int B, int N, int K,
                         int route, int32_t *idx, float *radius, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- registration of matched point sets and the per-round chain of ICP (no reference counterpart) ----
+ * Row-vector convention  s x R + T ~ y  ("Registration").  Per image b, over the KEPT rows i <
+ * lengths[b] (N without lengths) with weight w_i (1 without weights) and match y_i, the definition is part of the
+ * interface:
+ *   W = sum w;  xm, ym the weighted means;  C = sum w (x - xm)(y - ym)^T / W = U S V^T;
+ *   E = diag(1, 1, det(U V^T)), or I with allow_reflection;  R = U E V^T;
+ *   s = tr(S E) / (sum w |x - xm|^2 / W) with estimate_scale and a positive denominator, else 1;  T = ym - s xm R;
+ *   rmse = sqrt(max(0, s^2 var(x) - 2 s tr(S E) + var(y))), the weighted residual of (R, T, s) in closed form.
+ * W = 0 gives R = I, T = 0, s = 1, rmse = 0.  C = 0 gives R = I; a rank-deficient C gives a finite orthonormal R of
+ * the required determinant that attains the minimum residual (which one of several is not specified).  A non-finite
+ * coordinate or weight in a kept row makes R, T, s and rmse of THAT image NaN.
+ *   x [B,N,3] f32.  gather = 0: y [B,N,3] is matched row by row (M must equal N); idx [B,N] i32 or NULL then only
+ *   marks rows, idx < 0 = dropped.  gather = 1: y [B,M,3] is read at idx [B,N] (required); idx outside [0, M) = dropped,
+ *   and no gathered cloud is ever formed.  weights [B,N] f32 or NULL;  sqdist [B,N] f32 or NULL: a row is kept only
+ *   while sqdist <= max_sqdist;  lengths [B] i32 or NULL, clamped by the kernels; padded rows influence nothing.
+ *   R [B,3,3], T [B,3], s [B] f32 out;  rmse [B] f32 out or NULL.
+ * Two launches: eighteen float64 moments about a pivot (row 0 of x and of y) summed per workgroup over fixed chunks of
+ * 1024 rows into the workspace (B * ceil(N / 1024) * 144 bytes rounded up to 256) and then in a fixed order, no
+ * atomics -- the result of an image does not depend on the padding or the other images of its batch; then one lane per
+ * image in float64: a cyclic one-sided Jacobi SVD with a fixed sweep bound, rounded to float32 once at the end.
+ * ICP's bookkeeping, all three given or all NULL (rmse is then required): converged [B] i32, iterations [B] i32,
+ * prev_rmse [B] f64 (8-byte aligned), initialised by mr_align_icp_init.  An image with converged != 0 is left untouched,
+ * bit for bit.  Otherwise iterations += 1 and, with the float64 rmse before rounding: converged = 1 when rmse == 0 or,
+ * from the image's second round on, (prev_rmse - rmse) / prev_rmse <= relative_rmse_thr; prev_rmse = rmse.  W = 0
+ * then means "no kept match": converged = 1, rmse = 0, and R, T, s keep their values.
+ * mr_align_apply: xt [B,N,3] = s x R + T in float32, 0 in padded rows.  mr_align_closest_points: out [B,N,3] = the sum
+ * of bary * corner for mr_nearest_triangle_forward's (face [B,N], bary [B,N,3]), 0 where face is -1 or names a
+ * triangle with an index outside [0, V).  mr_align_icp_init: R0 / T0 / s0 (all given or all NULL: the identity) into
+ * R, T, s; rmse 0, converged 0, iterations 0.  All entry points only enqueue on `stream`: capturable in a HIP graph,
+ * nothing is read back.
+ * B, N, M, V, T as mr_nearest_forward / mr_nearest_triangle_forward take them (1 <= B <= 65535, 1..2^28 rows, B * rows
+ * < 2^36); anything else is MR_EINVAL (the query returns 0) before a device is touched. */
+size_t mr_align_workspace_bytes(int B, int N);
+int mr_align_solve(const float *x, const float *y, const int32_t *idx, int gather, const float *weights,
+                   const float *sqdist, float max_sqdist, const int32_t *lengths, int B, int N, int M,
+                   int estimate_scale, int allow_reflection, double relative_rmse_thr, float *R, float *T, float *s,
+                   float *rmse, int32_t *converged, int32_t *iterations, double *prev_rmse, void *workspace,
+                   size_t workspace_bytes, void *stream);
+int mr_align_apply(const float *x, const int32_t *lengths, const float *R, const float *T, const float *s, int B, int N,
+                   float *xt, void *stream);
+int mr_align_closest_points(const float *vertices, const int32_t *triangles, const int32_t *face, const float *bary,
+                            int B, int N, int V, int T, float *out, void *stream);
+int mr_align_icp_init(const float *R0, const float *T0, const float *s0, int B, float *R, float *T, float *s,
+                      float *rmse, int32_t *converged, int32_t *iterations, double *prev_rmse, void *stream);
+
 /* ---- point to nearest triangle: the point-to-mesh distance (no reference counterpart) ----
  * Per image b, for every query p_i with i < lengths[b], over the T triangles of one shared topology
  * ("Point-cloud losses"):

@@ -417,6 +417,21 @@ def lib():
         except AttributeError as e:   # the farthest-point entry points came without an ABI version bump
             raise NativeLibraryError("%s lacks the farthest-point sampling entry points (%s): rebuild it (make -C "
                                      "pytorch_mesh_renderer_amd/csrc)" % (LIB_PATH, e))
+        try:
+            L.mr_align_workspace_bytes.argtypes = [ci, ci]
+            L.mr_align_workspace_bytes.restype = sz
+            L.mr_align_solve.argtypes = ([vp, vp, vp, ci, vp, vp, cf, vp] + [ci] * 5 + [ctypes.c_double] + [vp] * 8
+                                         + [sz, vp])
+            L.mr_align_solve.restype = ci
+            L.mr_align_apply.argtypes = [vp] * 5 + [ci, ci, vp, vp]
+            L.mr_align_apply.restype = ci
+            L.mr_align_closest_points.argtypes = [vp] * 4 + [ci] * 4 + [vp, vp]
+            L.mr_align_closest_points.restype = ci
+            L.mr_align_icp_init.argtypes = [vp] * 3 + [ci] + [vp] * 8
+            L.mr_align_icp_init.restype = ci
+        except AttributeError as e:   # the registration entry points came without an ABI version bump
+            raise NativeLibraryError("%s lacks the registration entry points (%s): rebuild it (make -C "
+                                     "pytorch_mesh_renderer_amd/csrc)" % (LIB_PATH, e))
         _lib = L
     return _lib
 
@@ -1318,6 +1333,150 @@ def farthest_forward(points, K, lengths=None, start_idx=None, route=FARTHEST_ROU
         raise ValueError("the one-workgroup route of farthest-point sampling cannot hold %d points" % N)
     _check(rc, "mr_farthest_forward")
     return idx, radius
+
+
+def _chk_align(x, lengths, weights=None):
+    _chk("x", x, _F32, None, None, 3)
+    B, N, _ = x.shape
+    if not 1 <= B <= 65535 or not 1 <= N <= 1 << 28 or B * N >= 1 << 36:
+        raise ValueError("the registration kernels take 1..65535 images of 1..2^28 points, got %s" % list(x.shape))
+    if lengths is not None:
+        _chk("lengths", lengths, _I32, B)
+    if weights is not None:
+        _chk("weights", weights, _F32, B, N)
+    return B, N
+
+
+def align_solve(x, y, weights=None, lengths=None, idx=None, gather=False, sqdist=None, max_sqdist=float("inf"),
+                estimate_scale=False, allow_reflection=False):
+    """x [B,N,3] f32; y [B,N,3] matched row by row, or with gather y [B,M,3] read at idx [B,N] i32 (idx < 0 or >= M:
+    the row is dropped; without gather idx only marks rows); weights / sqdist [B,N] f32, lengths [B] i32 or None
+    (device) -> (R [B,3,3], T [B,3], s [B], rmse [B]) f32: mr_align_solve without ICP's bookkeeping."""
+    B, N = _chk_align(x, lengths, weights)
+    _chk("y", y, _F32, B, None if gather else N, 3)
+    M = y.shape[1]
+    if not 1 <= M <= 1 << 28 or B * M >= 1 << 36:
+        raise ValueError("the registration kernels take 1..65535 images of 1..2^28 points, got %s" % list(y.shape))
+    if gather and idx is None:
+        raise ValueError("gather needs idx")
+    for name, t, dtype in (("idx", idx, _I32), ("sqdist", sqdist, _F32)):
+        if t is not None:
+            _chk(name, t, dtype, B, N)
+    given = [t for t in (weights, lengths, idx, sqdist) if t is not None]
+    dev = _require_device(x, y, *given)
+    L = lib()
+    x, y = x.contiguous(), y.contiguous()
+    weights, lengths, idx, sqdist = (t.contiguous() if t is not None else None for t in (weights, lengths, idx, sqdist))
+    R = torch.empty(B, 3, 3, dtype=_F32, device=dev)
+    T = torch.empty(B, 3, dtype=_F32, device=dev)
+    s = torch.empty(B, dtype=_F32, device=dev)
+    rmse = torch.empty(B, dtype=_F32, device=dev)
+    with torch.cuda.device(dev):
+        ws, have = _workspace(dev, L.mr_align_workspace_bytes(B, N))
+        rc = L.mr_align_solve(_ptr(x), _ptr(y), _ptr(idx), 1 if gather else 0, _ptr(weights), _ptr(sqdist),
+                              float(max_sqdist), _ptr(lengths), B, N, M, 1 if estimate_scale else 0,
+                              1 if allow_reflection else 0, 0.0, _ptr(R), _ptr(T), _ptr(s), _ptr(rmse), None, None, None,
+                              _ptr(ws), have, _stream(dev))
+    _check(rc, "mr_align_solve")
+    return R, T, s, rmse
+
+
+def align_apply(x, R, T, s, lengths=None):
+    """x [B,N,3], R [B,3,3], T [B,3], s [B] f32, lengths [B] i32 or None (device) -> s x R + T [B,N,3], 0 in padded
+    rows: mr_align_apply."""
+    B, N = _chk_align(x, lengths)
+    _chk("R", R, _F32, B, 3, 3)
+    _chk("T", T, _F32, B, 3)
+    _chk("s", s, _F32, B)
+    dev = _require_device(x, R, T, s, *([lengths] if lengths is not None else []))
+    x, R, T, s = x.contiguous(), R.contiguous(), T.contiguous(), s.contiguous()
+    lengths = lengths.contiguous() if lengths is not None else None
+    xt = torch.empty_like(x)
+    with torch.cuda.device(dev):
+        rc = lib().mr_align_apply(_ptr(x), _ptr(lengths), _ptr(R), _ptr(T), _ptr(s), B, N, _ptr(xt), _stream(dev))
+    _check(rc, "mr_align_apply")
+    return xt
+
+
+def icp(x, y=None, mesh=None, x_lengths=None, y_lengths=None, init=None, max_iterations=100, relative_rmse_thr=1e-6,
+        estimate_scale=False, allow_reflection=False, max_sqdist=None, check_every=10):
+    """The rounds of iterative_closest_point on the device.  x [B,N,3] f32 against a cloud y [B,M,3] (y_lengths) or a
+    mesh = (vertices [B,V,3] f32, triangles [T,3] i32); init = (R, T, s) or None -> (converged [B] i32, rmse [B],
+    xt [B,N,3], R, T, s, iterations [B] i32).  A round is mr_align_apply, the search (mr_nearest_forward, or
+    mr_nearest_triangle_forward and mr_align_closest_points), mr_align_solve; every buffer is allocated before the
+    first round, and nothing is read back unless check_every > 0 (then `converged` every check_every rounds)."""
+    B, N = _chk_align(x, x_lengths)
+    if (y is None) == (mesh is None):
+        raise ValueError("exactly one of y and mesh must be given")
+    given = [t for t in (x_lengths, y_lengths) if t is not None]
+    if mesh is None:
+        B, N, M = _chk_clouds(x, y, x_lengths, y_lengths)
+        given.append(y)
+    else:
+        vertices, triangles = mesh
+        B, N, V, Tn = _chk_point_mesh(x, vertices, triangles, x_lengths)
+        given += [vertices, triangles]
+    if init is not None:
+        _chk("init R", init[0], _F32, B, 3, 3)
+        _chk("init T", init[1], _F32, B, 3)
+        _chk("init s", init[2], _F32, B)
+        given += list(init)
+    dev = _require_device(x, *given)
+    L = lib()
+    x = x.contiguous()
+    x_lengths = x_lengths.contiguous() if x_lengths is not None else None
+    y_lengths = y_lengths.contiguous() if y_lengths is not None else None
+    R0, T0, s0 = (t.contiguous() for t in init) if init is not None else (None, None, None)
+    R = torch.empty(B, 3, 3, dtype=_F32, device=dev)
+    T = torch.empty(B, 3, dtype=_F32, device=dev)
+    s = torch.empty(B, dtype=_F32, device=dev)
+    rmse = torch.empty(B, dtype=_F32, device=dev)
+    converged = torch.empty(B, dtype=_I32, device=dev)
+    iterations = torch.empty(B, dtype=_I32, device=dev)
+    prev_rmse = torch.empty(B, dtype=torch.float64, device=dev)
+    xt = torch.empty_like(x)
+    sqdist = torch.empty(B, N, dtype=_F32, device=dev)
+    idx = torch.empty(B, N, dtype=_I32, device=dev)
+    cut = float(max_sqdist) if max_sqdist is not None else float("inf")
+    cut_plane = sqdist if max_sqdist is not None else None
+    if mesh is None:
+        y = y.contiguous()
+        search_bytes = L.mr_nearest_workspace_bytes(B, N, M)
+    else:
+        vertices, triangles = vertices.contiguous(), triangles.contiguous()
+        bary = torch.empty(B, N, 3, dtype=_F32, device=dev)
+        closest = torch.empty(B, N, 3, dtype=_F32, device=dev)
+        search_bytes = L.mr_nearest_triangle_workspace_bytes(B, N, Tn)
+    stream = _stream(dev)
+    with torch.cuda.device(dev):
+        ws, have = _workspace(dev, max(search_bytes, L.mr_align_workspace_bytes(B, N)))
+        _check(L.mr_align_icp_init(_ptr(R0), _ptr(T0), _ptr(s0), B, _ptr(R), _ptr(T), _ptr(s), _ptr(rmse),
+                                   _ptr(converged), _ptr(iterations), _ptr(prev_rmse), stream), "mr_align_icp_init")
+        for round_ in range(max_iterations):
+            _check(L.mr_align_apply(_ptr(x), _ptr(x_lengths), _ptr(R), _ptr(T), _ptr(s), B, N, _ptr(xt), stream),
+                   "mr_align_apply")
+            if mesh is None:
+                _check(L.mr_nearest_forward(_ptr(xt), _ptr(y), _ptr(x_lengths), _ptr(y_lengths), B, N, M, _ptr(sqdist),
+                                            _ptr(idx), None, 1.0, 0, _ptr(ws), have, stream), "mr_nearest_forward")
+                target, gather, rows = y, 1, M
+            else:
+                _check(L.mr_nearest_triangle_forward(_ptr(xt), _ptr(vertices), _ptr(triangles), _ptr(x_lengths), B, N, V,
+                                                     Tn, _ptr(sqdist), _ptr(idx), _ptr(bary), None, _ptr(ws), have,
+                                                     stream), "mr_nearest_triangle_forward")
+                _check(L.mr_align_closest_points(_ptr(vertices), _ptr(triangles), _ptr(idx), _ptr(bary), B, N, V, Tn,
+                                                 _ptr(closest), stream), "mr_align_closest_points")
+                target, gather, rows = closest, 0, N
+            _check(L.mr_align_solve(_ptr(x), _ptr(target), _ptr(idx), gather, None, _ptr(cut_plane), cut,
+                                    _ptr(x_lengths), B, N, rows, 1 if estimate_scale else 0,
+                                    1 if allow_reflection else 0, float(relative_rmse_thr), _ptr(R), _ptr(T), _ptr(s),
+                                    _ptr(rmse), _ptr(converged), _ptr(iterations), _ptr(prev_rmse), _ptr(ws), have,
+                                    stream), "mr_align_solve")
+            if check_every and (round_ + 1) % check_every == 0 and round_ + 1 < max_iterations:
+                if bool((converged != 0).all()):   # the only read-back of the loop
+                    break
+        _check(L.mr_align_apply(_ptr(x), _ptr(x_lengths), _ptr(R), _ptr(T), _ptr(s), B, N, _ptr(xt), stream),
+               "mr_align_apply")
+    return converged, rmse, xt, R, T, s, iterations
 
 
 def nearest_triangle_plan(B, N, T):

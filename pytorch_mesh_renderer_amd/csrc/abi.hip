@@ -961,6 +961,51 @@ int mr_farthest_forward(const float *points, const int32_t *lengths, const int32
                                      (hipStream_t)stream);
 }
 
+size_t mr_align_workspace_bytes(int B, int N) {
+  if (bad_nearest_dims(B, N, 1)) return 0;
+  return mr::align_ws(B, N);
+}
+
+int mr_align_solve(const float *x, const float *y, const int32_t *idx, int gather, const float *weights,
+                   const float *sqdist, float max_sqdist, const int32_t *lengths, int B, int N, int M,
+                   int estimate_scale, int allow_reflection, double relative_rmse_thr, float *R, float *T, float *s,
+                   float *rmse, int32_t *converged, int32_t *iterations, double *prev_rmse, void *workspace,
+                   size_t workspace_bytes, void *stream) {
+  if (bad_nearest_dims(B, N, M)) return MR_EINVAL;
+  if (!x || !y || !R || !T || !s) return MR_EINVAL;
+  if (gather ? !idx : M != N) return MR_EINVAL;   // row by row: y has x's rows
+  const bool icp = converged != nullptr;
+  if ((iterations != nullptr) != icp || (prev_rmse != nullptr) != icp || (icp && !rmse)) return MR_EINVAL;
+  if (misaligned(prev_rmse, 8)) return MR_EINVAL;
+  const int rc = check_ws(workspace, workspace_bytes, mr::align_ws(B, N));
+  if (rc != MR_OK) return rc;
+  return mr::launch_align_solve(x, y, idx, gather != 0, weights, sqdist, max_sqdist, lengths, B, N, M,
+                                estimate_scale != 0, allow_reflection != 0, relative_rmse_thr, R, T, s, rmse, converged,
+                                iterations, prev_rmse, workspace, (hipStream_t)stream);
+}
+
+int mr_align_apply(const float *x, const int32_t *lengths, const float *R, const float *T, const float *s, int B, int N,
+                   float *xt, void *stream) {
+  if (bad_nearest_dims(B, N, 1)) return MR_EINVAL;
+  if (!x || !R || !T || !s || !xt) return MR_EINVAL;
+  return mr::launch_align_apply(x, lengths, R, T, s, B, N, xt, (hipStream_t)stream);
+}
+
+int mr_align_closest_points(const float *vertices, const int32_t *triangles, const int32_t *face, const float *bary,
+                            int B, int N, int V, int T, float *out, void *stream) {
+  if (bad_nearest_dims(B, N, T) || V < 1 || V > (1 << 28) || (size_t)B * V >= ((size_t)1 << 36)) return MR_EINVAL;
+  if (!vertices || !triangles || !face || !bary || !out) return MR_EINVAL;
+  return mr::launch_align_closest_points(vertices, triangles, face, bary, B, N, V, T, out, (hipStream_t)stream);
+}
+
+int mr_align_icp_init(const float *R0, const float *T0, const float *s0, int B, float *R, float *T, float *s,
+                      float *rmse, int32_t *converged, int32_t *iterations, double *prev_rmse, void *stream) {
+  if (B < 1 || B > 65535) return MR_EINVAL;
+  if (!R || !T || !s || !rmse || !converged || !iterations || !prev_rmse || misaligned(prev_rmse, 8)) return MR_EINVAL;
+  if ((R0 != nullptr) != (T0 != nullptr) || (R0 != nullptr) != (s0 != nullptr)) return MR_EINVAL;
+  return mr::launch_align_icp_init(R0, T0, s0, B, R, T, s, rmse, converged, iterations, prev_rmse, (hipStream_t)stream);
+}
+
 inline bool bad_knn_dims(int B, int N, int M, int K) {
   return bad_nearest_dims(B, N, M) || K < 1 || K > mr::knn_max_k() || (size_t)N * K > (size_t)INT_MAX ||
          (size_t)B * N * K >= ((size_t)1 << 36);

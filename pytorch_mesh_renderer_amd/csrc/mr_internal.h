@@ -291,6 +291,19 @@ void farthest_plan(int B, int N, int K, int *route, int *workgroup, int *points_
 size_t farthest_ws(int B, int N, int K);
 int launch_farthest_forward(const float *points, const int32_t *lengths, const int32_t *start_idx, int B, int N, int K,
                             int route, int32_t *idx, float *radius, void *ws, hipStream_t s);
+// registration of matched point sets and ICP's per-round chain, mr_align_* (align.hip)
+size_t align_ws(int B, int N);
+int launch_align_solve(const float *x, const float *y, const int32_t *idx, int gather, const float *weights,
+                       const float *sqdist, float max_sqdist, const int32_t *lengths, int B, int N, int M,
+                       int estimate_scale, int allow_reflection, double relative_rmse_thr, float *R, float *T, float *s,
+                       float *rmse, int32_t *converged, int32_t *iterations, double *prev_rmse, void *ws,
+                       hipStream_t stream);
+int launch_align_apply(const float *x, const int32_t *lengths, const float *R, const float *T, const float *s, int B,
+                       int N, float *xt, hipStream_t stream);
+int launch_align_closest_points(const float *vertices, const int32_t *triangles, const int32_t *face, const float *bary,
+                                int B, int N, int V, int T, float *out, hipStream_t stream);
+int launch_align_icp_init(const float *R0, const float *T0, const float *s0, int B, float *R, float *T, float *s,
+                          float *rmse, int32_t *converged, int32_t *iterations, double *prev_rmse, hipStream_t stream);
 // point to nearest triangle, mr_nearest_triangle_* (nearest.hip)
 void nearest_triangle_plan(int B, int N, int T, int *splits, int *queries_per_lane, int *triangle_tile, int *workgroup);
 size_t nearest_triangle_ws(int B, int N, int T);

@@ -14,8 +14,13 @@ knn_points is the K-neighbour form of nearest_points (a sorted list of K keys pe
 split between the two paths), knn_gather reads values at its indices, and estimate_point_normals is its first
 consumer: the normals of a scan from the covariance of every point's neighbourhood.  sample_farthest_points thins a
 cloud to K well-spread points before any of these O(N M) searches (csrc/farthest.hip on a HIP device, a torch loop
-of K steps elsewhere; both follow one bit-exact definition).
+of K steps elsewhere; both follow one bit-exact definition).  corresponding_points_alignment and
+iterative_closest_point bring a scan that arrives in its sensor's frame -- rotated, shifted, at another scale -- into
+the mesh's frame first: the least-squares similarity between matched points, and ICP around the module's own searches
+against a cloud or against the mesh itself (csrc/align.hip; INTEGRATION.md, "Registration").
 """
+import collections
+
 import torch
 from torch.autograd.function import once_differentiable
 
@@ -854,3 +859,253 @@ def point_mesh_face_distance(points, vertices, triangles, lengths=None):
     a mesh under PyTorch3D's name, each a mean of its own (over the valid points, over the usable triangles)."""
     return (point_mesh_distance(points, vertices, triangles, lengths)
             + mesh_point_distance(points, vertices, triangles, lengths))
+
+
+# ---- registration: the similarity transform between matched points, and ICP ---------------------------------------------
+
+SimilarityTransform = collections.namedtuple("SimilarityTransform", ["R", "T", "s"])
+ICPSolution = collections.namedtuple("ICPSolution", ["converged", "rmse", "Xt", "RTs", "iterations"])
+
+
+def _alignment_torch(x, y, weights, lengths, estimate_scale, allow_reflection):
+    """corresponding_points_alignment's definition on the device and in the dtype of x [B,N,3] / y [B,N,3], with
+    torch.linalg.svd and ordinary autograd -> (R [B,3,3], T [B,3], s [B], mean squared residual [B])."""
+    B, N, _ = x.shape
+    w = weights if weights is not None else x.new_ones(B, N)
+    if lengths is not None:
+        valid = torch.arange(N, device=x.device)[None, :] < lengths[:, None]
+        w = torch.where(valid, w, torch.zeros_like(w))
+        x = torch.where(valid[..., None], x, torch.zeros_like(x))   # padded coordinates influence nothing, NaN included
+        y = torch.where(valid[..., None], y, torch.zeros_like(y))
+    W = w.sum(1)
+    empty = ~(W > 0) & (W == W)   # (a NaN weight is not "empty": it makes the image NaN)
+    iw = 1.0 / torch.where(empty, torch.ones_like(W), W)
+    # the means about a pivot (row 0, as the kernels do): coincident points then have a variance of exactly 0
+    finite_or_zero = lambda t: torch.where(torch.isfinite(t), t, torch.zeros_like(t))
+    px, py = finite_or_zero(x[:, :1].detach()), finite_or_zero(y[:, :1].detach())
+    xm = px[:, 0] + (w[..., None] * (x - px)).sum(1) * iw[:, None]
+    ym = py[:, 0] + (w[..., None] * (y - py)).sum(1) * iw[:, None]
+    xc, yc = x - xm[:, None], y - ym[:, None]
+    C = torch.einsum("bn,bni,bnj->bij", w, xc, yc) * iw[:, None, None]
+    var_x = (w * (xc * xc).sum(-1)).sum(1) * iw
+    eye = torch.eye(3, dtype=x.dtype, device=x.device).expand(B, 3, 3)
+    # a non-finite coordinate or weight: the image's outputs are NaN (and torch.linalg.svd never sees it)
+    poisoned = ~torch.isfinite(C.detach()).all(-1).all(-1) | ~torch.isfinite(var_x.detach())
+    degenerate = empty | (C.detach().abs().amax(dim=(1, 2)) == 0)    # W = 0, or C = 0: R = I
+    U, S, Vh = torch.linalg.svd(torch.where((degenerate | poisoned)[:, None, None], eye, C))
+    if allow_reflection:
+        last = torch.ones_like(W)
+    else:
+        last = torch.where(torch.det(U.detach() @ Vh.detach()) < 0, -torch.ones_like(W), torch.ones_like(W))
+    E = torch.stack([torch.ones_like(last), torch.ones_like(last), last], dim=-1)
+    R = torch.where(degenerate[:, None, None], eye, (U * E[:, None, :]) @ Vh)
+    trace = torch.where(degenerate, torch.zeros_like(W), (S * E).sum(-1))
+    if estimate_scale:
+        usable = var_x > 0
+        s = torch.where(usable, trace / torch.where(usable, var_x, torch.ones_like(var_x)), torch.ones_like(W))
+    else:
+        s = torch.ones_like(W)
+    T = torch.where(empty[:, None], torch.zeros_like(ym), ym - s[:, None] * torch.einsum("bi,bij->bj", xm, R))
+    residual = s[:, None, None] * (xc @ R) - yc
+    mse = (w * (residual * residual).sum(-1)).sum(1) * iw
+    nan = torch.full_like(W, float("nan"))
+    R = torch.where(poisoned[:, None, None], nan[:, None, None], R)
+    T = torch.where(poisoned[:, None], nan[:, None], T)
+    s = torch.where(poisoned, nan, s)
+    return R, T, s, mse
+
+
+def _alignment_arguments(x, y, weights, lengths):
+    _cloud("x", x)
+    _cloud("y", y)
+    if x.shape != y.shape:
+        raise ValueError("x and y must have the same shape (they are matched row by row), got %s and %s"
+                         % (list(x.shape), list(y.shape)))
+    if x.device != y.device:
+        raise RuntimeError("x and y must be on the same device")
+    if x.dtype != y.dtype:
+        raise RuntimeError("x and y must have the same dtype, got %s and %s" % (x.dtype, y.dtype))
+    single = x.dim() == 2
+    if single:
+        x, y = x.unsqueeze(0), y.unsqueeze(0)
+        weights = weights.unsqueeze(0) if torch.is_tensor(weights) and weights.dim() == 1 else weights
+        lengths = lengths.reshape(1) if torch.is_tensor(lengths) and lengths.dim() == 0 else lengths
+    B, N, _ = x.shape
+    if B < 1:
+        raise ValueError("x must hold at least one image, got %s" % list(x.shape))
+    if weights is not None:
+        if not torch.is_tensor(weights) or not weights.is_floating_point():
+            raise TypeError("weights must be a floating-point tensor")
+        if weights.shape != (B, N):
+            raise ValueError("weights must have shape [%d, %d], got %s" % (B, N, list(weights.shape)))
+        if weights.device != x.device:
+            raise RuntimeError("weights must be on the clouds' device")
+        if weights.dtype != x.dtype:
+            raise RuntimeError("weights must have the clouds' dtype, got %s and %s" % (weights.dtype, x.dtype))
+    return x, y, weights, _lengths("lengths", lengths, B, N, x), single
+
+
+def corresponding_points_alignment(x, y, weights=None, lengths=None, estimate_scale=False, allow_reflection=False):
+    """x, y [B,N,3] (or [N,3]: one image, results without the batch axis), matched row by row -> SimilarityTransform(
+    R [B,3,3], T [B,3], s [B]) with s * x @ R + T ~ y (PyTorch3D's name and row-vector convention): the weighted
+    least-squares similarity (Umeyama).  weights [B,N] >= 0 optional; lengths [B] as everywhere in this module
+    (clamped on the device, padded rows influence nothing).  The definition is part of the interface:
+
+      W = sum w; xm, ym the weighted means; C = sum w (x - xm)(y - ym)^T / W = U S V^T;
+      E = diag(1, 1, det(U V^T)), or I with allow_reflection; R = U E V^T;
+      s = tr(S E) / (sum w |x - xm|^2 / W) with estimate_scale, else 1; T = ym - s xm R.
+
+    W = 0 (an empty image, all weights 0) gives R = I, T = 0, s = 1; zero variance of x gives s = 1; C = 0 gives
+    R = I; a rank-deficient C (collinear or coincident points) gives a finite orthonormal R of the required
+    determinant whose residual is the minimum -- which of the equal minimisers is not specified.  A non-finite
+    coordinate in a valid row makes that image's outputs non-finite and touches no other image.
+
+    float32 device tensors none of which requires a gradient go through csrc/align.hip (float64 moments in a fixed
+    order, one Jacobi SVD per image in float64, rounded once; bitwise reproducible, capturable).  Inputs that require
+    a gradient, host tensors and other dtypes take the torch spelling: the definition above in the inputs' dtype with
+    torch.linalg.svd and ordinary autograd."""
+    x, y, weights, lengths, single = _alignment_arguments(x, y, weights, lengths)
+    needs_grad = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, y, weights))
+    if _on_hip_path(x) and not needs_grad:
+        R, T, s, _ = _native.align_solve(x.detach(), y.detach(), weights.detach() if weights is not None else None,
+                                         lengths, estimate_scale=bool(estimate_scale),
+                                         allow_reflection=bool(allow_reflection))
+    else:
+        R, T, s, _ = _alignment_torch(x, y, weights, lengths, bool(estimate_scale), bool(allow_reflection))
+    return SimilarityTransform(R[0], T[0], s[0]) if single else SimilarityTransform(R, T, s)
+
+
+def _closest_points_torch(xt, v, tris, lengths):
+    """-> (sqdist [B,N], kept [B,N] bool, the closest point of the nearest triangle [B,N,3])."""
+    sqdist, face, bary = _nearest_triangles_torch(xt, v, tris, lengths)
+    corner = tris.clamp(0, v.shape[1] - 1)[face.long().clamp(min=0)]                      # [B,N,3]
+    corners = torch.stack([torch.gather(v, 1, corner[..., k, None].expand(-1, -1, 3)) for k in range(3)], dim=2)
+    return sqdist, face >= 0, (bary[..., None] * corners).sum(2)
+
+
+def _icp_torch(x, target, x_lengths, y_lengths, init, max_iterations, relative_rmse_thr, estimate_scale,
+               allow_reflection, max_sqdist, check_every):
+    """iterative_closest_point's rounds in torch ops on the device and in the dtype of x, image by image frozen as the
+    kernels freeze them (the flags live on the device here too)."""
+    B, N, _ = x.shape
+    dev, dtype = x.device, x.dtype
+    if init is None:
+        R, T, s = torch.eye(3, dtype=dtype, device=dev).repeat(B, 1, 1), x.new_zeros(B, 3), x.new_ones(B)
+    else:
+        R, T, s = (t.clone() for t in init)
+    n_valid = x_lengths.long() if x_lengths is not None else torch.full((B,), N, dtype=torch.int64, device=dev)
+    valid = torch.arange(N, device=dev)[None, :] < n_valid[:, None]
+    x = torch.where(valid[..., None], x, torch.zeros_like(x))
+    apply = lambda: torch.where(valid[..., None], s[:, None, None] * (x @ R) + T[:, None, :], torch.zeros_like(x))
+    rmse, prev = x.new_zeros(B), x.new_zeros(B)
+    converged = torch.zeros(B, dtype=torch.bool, device=dev)
+    iterations = torch.zeros(B, dtype=torch.int32, device=dev)
+    for round_ in range(max_iterations):
+        xt = apply()
+        if target[0] == "cloud":
+            sqdist, idx = _nearest_torch(xt, target[1], x_lengths, y_lengths)
+            kept = idx >= 0
+            match = torch.gather(target[1], 1, idx.long().clamp(min=0)[..., None].expand(-1, -1, 3))
+        else:
+            sqdist, kept, match = _closest_points_torch(xt, target[1], target[2], x_lengths)
+        if max_sqdist is not None:
+            kept = kept & (sqdist <= max_sqdist)
+        kept = kept & valid
+        match = torch.where(kept[..., None], match, torch.zeros_like(match))
+        nR, nT, ns, mse = _alignment_torch(torch.where(kept[..., None], x, torch.zeros_like(x)), match, kept.to(dtype),
+                                           None, estimate_scale, allow_reflection)
+        root = mse.clamp(min=0).sqrt()
+        nothing = ~kept.any(dim=1)
+        live = ~converged
+        change = live & ~nothing
+        R = torch.where(change[:, None, None], nR, R)
+        T = torch.where(change[:, None], nT, T)
+        s = torch.where(change, ns, s)
+        rmse = torch.where(live, torch.where(nothing, torch.zeros_like(root), root), rmse)
+        iterations = iterations + live.to(torch.int32)
+        done = nothing | (root == 0) | ((iterations >= 2) & ((prev - root) / prev <= relative_rmse_thr))
+        prev = torch.where(live, rmse, prev)
+        converged = converged | (live & done)
+        if check_every and (round_ + 1) % check_every == 0 and round_ + 1 < max_iterations and bool(converged.all()):
+            break
+    return converged, rmse, apply(), R, T, s, iterations
+
+
+def iterative_closest_point(x, y, x_lengths=None, y_lengths=None, init_transform=None, max_iterations=100,
+                            relative_rmse_thr=1e-6, estimate_scale=False, allow_reflection=False,
+                            max_correspondence_distance=None, check_every=10):
+    """Registers the cloud x [B,N,3] (or [N,3]: one image, results without the batch axis) to y: a cloud [B,M,3], or a
+    mesh (vertices [B,V,3], triangles [T,3] integer, one topology for the batch) -> ICPSolution(converged [B] bool,
+    rmse [B], Xt [B,N,3], RTs SimilarityTransform(R, T, s), iterations [B] int32), PyTorch3D's name and row-vector
+    convention s * x @ R + T ~ y.  For a mesh the match of a point is its closest point on the nearest triangle
+    (nearest_triangles' sum of bary * corner): the surface itself, without the sampling noise at which ICP against
+    sampled points stalls.
+
+    One round, per image: Xt = s x R + T; search Xt -> y; keep the matches with sqdist <= max_correspondence_distance^2
+    (all of them without one); solve corresponding_points_alignment of the ORIGINAL x to the kept matches, so rounding
+    never accumulates over rounds; rmse = the root of the mean squared residual of the new transform on those matches.
+    The image has converged when rmse == 0 or, from its second round on, (prev_rmse - rmse) / prev_rmse <=
+    relative_rmse_thr; an image with no kept match converges at once with its transform unchanged and rmse 0.
+
+    Convergence is per image and on the device: once an image has converged, its R, T, s, rmse and iterations never
+    change again, bit for bit, whatever the other images of the batch do -- a batched call equals the single-image
+    calls.  The host reads the flags back only every check_every rounds, to stop early; check_every=0 never reads
+    anything back and runs exactly max_iterations rounds, which is the form torch.cuda.graph can capture.  Xt is the
+    original cloud under the returned transform, 0 in padded rows.  init_transform: a SimilarityTransform (or any
+    (R, T, s)) to start from, the identity without one.  x_lengths, y_lengths as in nearest_points (a mesh target
+    takes no y_lengths).  PyTorch3D's t_history and verbose are not offered.
+
+    The outputs are NOT differentiable and carry no graph.  float32 device tensors run csrc/align.hip around the
+    module's own searches (apply, search, moments, solve: a fixed chain of launches per round, every buffer allocated
+    before the first round, bitwise reproducible); host tensors and other dtypes take the same rounds in torch ops."""
+    _cloud("x", x)
+    for name, value in (("max_iterations", max_iterations), ("check_every", check_every)):
+        if not isinstance(value, int) or isinstance(value, bool) or value < 0:
+            raise ValueError("%s must be an int >= 0, got %r" % (name, value))
+    if max_correspondence_distance is not None and not float(max_correspondence_distance) >= 0:
+        raise ValueError("max_correspondence_distance must be >= 0, got %r" % (max_correspondence_distance,))
+    is_mesh = isinstance(y, (tuple, list))
+    with torch.no_grad():
+        if is_mesh:
+            if len(y) != 2:
+                raise ValueError("a mesh target is (vertices, triangles), got %d entries" % len(y))
+            if y_lengths is not None:
+                raise ValueError("a mesh target takes no y_lengths")
+            p, v, tris, x_lengths, single = _point_mesh_arguments(x.detach(), y[0].detach() if torch.is_tensor(y[0])
+                                                                  else y[0], y[1], x_lengths)
+            target = ("mesh", v, tris)
+        else:
+            p, cloud, x_lengths, y_lengths, single = _arguments(x.detach(), y.detach() if torch.is_tensor(y) else y,
+                                                                x_lengths, y_lengths)
+            target = ("cloud", cloud)
+        B = p.shape[0]
+        init = None
+        if init_transform is not None:
+            if len(init_transform) != 3 or not all(torch.is_tensor(t) for t in init_transform):
+                raise ValueError("init_transform must be (R, T, s) tensors")
+            R0, T0, s0 = (t.detach() for t in init_transform)
+            if single and R0.dim() == 2:
+                R0, T0, s0 = R0.unsqueeze(0), T0.unsqueeze(0), s0.reshape(1)
+            if R0.shape != (B, 3, 3) or T0.shape != (B, 3) or s0.shape != (B,):
+                raise ValueError("init_transform must hold R [%d, 3, 3], T [%d, 3] and s [%d], got %s, %s and %s"
+                                 % (B, B, B, list(R0.shape), list(T0.shape), list(s0.shape)))
+            if any(t.device != p.device for t in (R0, T0, s0)):
+                raise RuntimeError("init_transform must be on the clouds' device")
+            if any(t.dtype != p.dtype for t in (R0, T0, s0)):
+                raise RuntimeError("init_transform must have the clouds' dtype")
+            init = (R0, T0, s0)
+        cut = float(max_correspondence_distance) ** 2 if max_correspondence_distance is not None else None
+        if _on_hip_path(p):
+            on_device = dict(y=target[1]) if not is_mesh else dict(mesh=(target[1], _device_triangles(tris, v.shape[1])))
+            converged, rmse, xt, R, T, s, iterations = _native.icp(
+                p, x_lengths=x_lengths, y_lengths=y_lengths, init=init, max_iterations=max_iterations,
+                relative_rmse_thr=float(relative_rmse_thr), estimate_scale=bool(estimate_scale),
+                allow_reflection=bool(allow_reflection), max_sqdist=cut, check_every=check_every, **on_device)
+            converged = converged != 0
+        else:
+            converged, rmse, xt, R, T, s, iterations = _icp_torch(
+                p, target, x_lengths, y_lengths, init, max_iterations, float(relative_rmse_thr), bool(estimate_scale),
+                bool(allow_reflection), cut, check_every)
+    if single:
+        return ICPSolution(converged[0], rmse[0], xt[0], SimilarityTransform(R[0], T[0], s[0]), iterations[0])
+    return ICPSolution(converged, rmse, xt, SimilarityTransform(R, T, s), iterations)
