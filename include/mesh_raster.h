@@ -868,6 +868,56 @@ size_t mr_farthest_workspace_bytes(int B, int N, int K);
 int mr_farthest_forward(const float *points, const int32_t *lengths, const int32_t *start_idx, int B, int N, int K,
                         int route, int32_t *idx, float *radius, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- (I + lam L) over a mesh's adjacency: apply and conjugate-gradient solve (no reference counterpart) ----
+ * A = I + lam L with L = D - Adj the combinatorial graph Laplacian of a symmetric CSR adjacency (nbr_offsets [V+1],
+ * nbr [nnz] i32, as mesh_topology() builds it; INTEGRATION.md, "Preconditioned optimisation"):
+ *   (A x)_i = (1 + lam deg_i) x_i - lam sum_{j in nbr(i)} x_j;   a vertex without neighbours has the identity row.
+ * A is symmetric positive definite with smallest eigenvalue 1.  x, y, b, x0 are [B,V,C] f32 with 1 <= C <= 4, one
+ * adjacency for the batch; every (image, channel) pair is a system of its own.  Offsets are clamped into [0, nnz] and
+ * a neighbour outside [0, V) adds nothing, whatever the arrays hold.
+ * mr_laplacian_apply: y = A x, one launch; the row is evaluated in float64 -- the neighbours summed in CSR order,
+ * then (1 + lam deg_i) x_i - lam sum -- and rounded to float32 once.  The solve's q = A p is the same evaluation.
+ * mr_laplacian_solve: x with A x = b by Jacobi-preconditioned conjugate gradients.  The algorithm is part of the
+ * interface.  M = diag(1 + lam deg);  x = x0 (NULL: 0), r = b - A x, z = r / M, p = z, rho = r.z;  per iteration
+ *   q = A p;  alpha = rho / p.q;  x += alpha p;  r -= alpha q;  z = r / M;  rho' = r.z;  p = z + (rho' / rho) p.
+ * The vectors are float32; the dot products, alpha, beta and every row of A p are float64, rounded once where they meet
+ * the vectors.
+ * A system FREEZES the first time one of these holds, after which its x, iterations and residual never change again,
+ * bit for bit, whatever the other systems of the call do:
+ *   1. r.r <= tol^2 b.b, tested before the first iteration and after every one (b = 0 without x0: x = 0, 0 iterations);
+ *   2. b.b or the initial r.r is not finite: the system's x is all NaN, 0 iterations, residual NaN;
+ *   3. p.q <= 0 or not finite (breakdown): the system keeps the x it had before that iteration.
+ *   iterations [B,C] i32 out: iterations performed;  residual [B,C] f32 out: sqrt(r.r / b.b) of the recurrence when
+ *   the system froze or the iterations ran out, 0 for b = 0.
+ * The order of every sum depends on (V, C, route) alone: a batch equals its single calls and a run with more
+ * iterations equals the shorter one wherever that had frozen, bit for bit.  Two routes.  Route 1: one launch, one
+ * workgroup of `workgroup_size` lanes per image holding `vertices_per_lane` vertices a lane in registers, p published
+ * through LDS (V <= 3072).  Route 2: `slices` workgroups per image; one launch before the first iteration, two per
+ * iteration and one at the end, partial dot products in the workspace summed by every workgroup of the next launch;
+ * stream order is the only synchronisation between workgroups.  mr_laplacian_solve_plan: the route and launch shape
+ * for `route` (0: the library's choice, a function of V and C alone; 1 / 2 forced; a forced route 1 that cannot hold
+ * V is MR_EINVAL), a pure host function.
+ * A call runs the iterations [first_iteration, first_iteration + iteration_count) cut at max_iterations: with
+ * first_iteration = 0 it starts the solve, and when the range reaches max_iterations it ends it (iterations,
+ * residual and rule 2's NaN are written then).  A range that stops short writes all_frozen [B] i32 (when given):
+ * whether every system of image b is frozen, for a caller that reads it back to stop early -- by calling once more
+ * with first_iteration = max_iterations.  Route 1 runs every iteration in the call with first_iteration = 0 and does
+ * nothing in any other.  (0, max_iterations, NULL) is the whole solve, nothing read back.  The workspace (five
+ * [B,V,C] f32 planes, the partials and the systems' state; needed by every call, it carries the solve between the
+ * calls of one solve) serves either route.  All entry points only enqueue on `stream`: capturable in a HIP graph.
+ * 1 <= B <= 65535, 1 <= V < 2^28, B V C < 2^36, nnz >= 0, lam >= 0 and finite, tol >= 0 and finite,
+ * 0 <= max_iterations <= 10000, 0 <= first_iteration <= max_iterations; anything else is MR_EINVAL (the workspace
+ * query returns 0) before a device is touched. */
+int mr_laplacian_apply(const float *x, const int32_t *nbr_offsets, const int32_t *nbr, int B, int V, int C, int nnz,
+                       float lam, float *y, void *stream);
+int mr_laplacian_solve_plan(int V, int C, int route, int *chosen_route, int *workgroup_size, int *vertices_per_lane,
+                            int *slices);
+size_t mr_laplacian_solve_workspace_bytes(int B, int V, int C);
+int mr_laplacian_solve(const float *b, const float *x0, const int32_t *nbr_offsets, const int32_t *nbr, int B, int V,
+                       int C, int nnz, float lam, double tol, int max_iterations, int route, int first_iteration,
+                       int iteration_count, int32_t *all_frozen, float *x, int32_t *iterations, float *residual,
+                       void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- registration of matched point sets and the per-round chain of ICP (no reference counterpart) ----
  * Row-vector convention  s x R + T ~ y  ("Registration").  Per image b, over the KEPT rows i <
  * lengths[b] (N without lengths) with weight w_i (1 without weights) and match y_i, the definition is part of the

@@ -418,6 +418,19 @@ def lib():
             raise NativeLibraryError("%s lacks the farthest-point sampling entry points (%s): rebuild it (make -C "
                                      "pytorch_mesh_renderer_amd/csrc)" % (LIB_PATH, e))
         try:
+            L.mr_laplacian_apply.argtypes = [vp] * 3 + [ci] * 4 + [cf, vp, vp]
+            L.mr_laplacian_apply.restype = ci
+            L.mr_laplacian_solve_plan.argtypes = [ci] * 3 + [vp] * 4
+            L.mr_laplacian_solve_plan.restype = ci
+            L.mr_laplacian_solve_workspace_bytes.argtypes = [ci] * 3
+            L.mr_laplacian_solve_workspace_bytes.restype = sz
+            L.mr_laplacian_solve.argtypes = ([vp] * 4 + [ci] * 4 + [cf, ctypes.c_double] + [ci] * 4 + [vp] * 5
+                                             + [sz, vp])
+            L.mr_laplacian_solve.restype = ci
+        except AttributeError as e:   # the Laplacian solve entry points came without an ABI version bump
+            raise NativeLibraryError("%s lacks the Laplacian solve entry points (%s): rebuild it (make -C "
+                                     "pytorch_mesh_renderer_amd/csrc)" % (LIB_PATH, e))
+        try:
             L.mr_align_workspace_bytes.argtypes = [ci, ci]
             L.mr_align_workspace_bytes.restype = sz
             L.mr_align_solve.argtypes = ([vp, vp, vp, ci, vp, vp, cf, vp] + [ci] * 5 + [ctypes.c_double] + [vp] * 8
@@ -1333,6 +1346,102 @@ def farthest_forward(points, K, lengths=None, start_idx=None, route=FARTHEST_ROU
         raise ValueError("the one-workgroup route of farthest-point sampling cannot hold %d points" % N)
     _check(rc, "mr_farthest_forward")
     return idx, radius
+
+
+LAPLACIAN_ROUTE_PLAN, LAPLACIAN_ROUTE_RESIDENT, LAPLACIAN_ROUTE_STEPS = 0, 1, 2   # mr_laplacian_solve's `route`
+_LAPLACIAN_TAKES = "1..2^28 - 1 vertices and 1..4 channels"
+
+
+def laplacian_solve_plan(V, C, route=None):
+    """The route and launch shape mr_laplacian_solve takes for V vertices and C channels, a pure host function of
+    the two: {"route" (1: one launch, the image in one workgroup's registers; 2: two launches per iteration),
+    "workgroup_size", "vertices_per_lane"} (include/mesh_raster.h).  route forces one; a forced resident route that
+    cannot hold V is a ValueError."""
+    plan = _plan("laplacian_solve_plan", (V, C, route or 0), ("route", "workgroup_size", "vertices_per_lane", "slices"),
+                 _LAPLACIAN_TAKES + " on a route that holds them")
+    del plan["slices"]
+    return plan
+
+
+def _chk_laplacian(x, topology, lam, name="x"):
+    _chk(name, x, _F32, None, None, None)
+    B, V, C = x.shape
+    if not isinstance(topology, MeshTopology) or topology.vertex_count != V:
+        raise ValueError("topology must be the mesh_topology() of the triangles and of these %d vertices" % V)
+    if not 1 <= B <= 65535 or not 1 <= V < 1 << 28 or not 1 <= C <= 4 or B * V * C >= 1 << 36:
+        raise ValueError("the Laplacian solve takes 1..65535 images of %s, got %s" % (_LAPLACIAN_TAKES, list(x.shape)))
+    lam = float(lam)
+    if not 0.0 <= lam < float("inf"):
+        raise ValueError("lam must be a finite number >= 0, got %r" % (lam,))
+    _chk("neighbour offsets", topology.nbr_offsets, _I32, V + 1)
+    _chk("neighbours", topology.nbr, _I32, 2 * topology.edge_count)
+    return B, V, C, lam
+
+
+def laplacian_apply(x, topology, lam):
+    """x [B,V,C] f32 (device), topology: mesh_topology() of these V vertices -> (I + lam L) x: mr_laplacian_apply."""
+    B, V, C, lam = _chk_laplacian(x, topology, lam)
+    dev = _require_device(x, topology.nbr_offsets, topology.nbr)
+    x = x.contiguous()
+    y = torch.empty_like(x)
+    with torch.cuda.device(dev):
+        rc = lib().mr_laplacian_apply(_ptr(x), _ptr(topology.nbr_offsets), _ptr(topology.nbr), B, V, C,
+                                      topology.nbr.shape[0], lam, _ptr(y), _stream(dev))
+    _check(rc, "mr_laplacian_apply")
+    return y
+
+
+def laplacian_solve(b, topology, lam, tol=1e-6, max_iterations=300, x0=None, check_every=0, route=None):
+    """b [B,V,C] f32 (device), x0 the same or None -> (x, iterations [B,C] i32, residual [B,C] f32) with
+    (I + lam L) x = b: mr_laplacian_solve.  check_every = 0 enqueues the whole solve and reads nothing back; k > 0
+    reads one word every k iterations of the stepped route and stops launching once every system is frozen (the
+    resident route leaves its loop by itself).  route: None, or LAPLACIAN_ROUTE_RESIDENT / _STEPS forced (a forced
+    resident route that cannot hold V is a ValueError)."""
+    B, V, C, lam = _chk_laplacian(b, topology, lam, "b")
+    tol, max_iterations, check_every = float(tol), int(max_iterations), int(check_every)
+    if not 0.0 <= tol < float("inf"):
+        raise ValueError("tol must be a finite number >= 0, got %r" % (tol,))
+    if not 0 <= max_iterations <= 10000:
+        raise ValueError("max_iterations must lie in 0..10000, got %r" % (max_iterations,))
+    if check_every < 0:
+        raise ValueError("check_every must be >= 0, got %r" % (check_every,))
+    if route not in (None, LAPLACIAN_ROUTE_PLAN, LAPLACIAN_ROUTE_RESIDENT, LAPLACIAN_ROUTE_STEPS):
+        raise ValueError("route must be None, 1 (resident) or 2 (stepped), got %r" % (route,))
+    if x0 is not None:
+        _chk("x0", x0, _F32, B, V, C)
+    dev = _require_device(b, topology.nbr_offsets, topology.nbr, *([x0] if x0 is not None else []))
+    if check_every and torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("check_every > 0 reads back from the device, which a stream capture cannot do: "
+                           "capture the solve with check_every=0")
+    stepped = laplacian_solve_plan(V, C, route)["route"] == LAPLACIAN_ROUTE_STEPS   # (ValueError: a forced route 1)
+    L = lib()
+    b = b.contiguous()
+    x0 = x0.contiguous() if x0 is not None else None
+    x = torch.empty_like(b)
+    iterations = torch.empty(B, C, dtype=_I32, device=dev)
+    residual = torch.empty(B, C, dtype=_F32, device=dev)
+    chunk = check_every if stepped and check_every else max(max_iterations, 1)
+    all_frozen = torch.empty(B, dtype=_I32, device=dev) if chunk < max_iterations else None
+    with torch.cuda.device(dev):
+        ws, have = _workspace(dev, L.mr_laplacian_solve_workspace_bytes(B, V, C))
+        stream = _stream(dev)
+
+        def run(first, count):
+            _check(L.mr_laplacian_solve(_ptr(b), _ptr(x0), _ptr(topology.nbr_offsets), _ptr(topology.nbr), B, V, C,
+                                        topology.nbr.shape[0], lam, tol, max_iterations, int(route or 0), first, count,
+                                        _ptr(all_frozen), _ptr(x), _ptr(iterations), _ptr(residual), _ptr(ws), have,
+                                        stream), "mr_laplacian_solve")
+
+        first = 0
+        while True:
+            run(first, chunk)
+            first += chunk
+            if first >= max_iterations:
+                break
+            if bool((all_frozen != 0).all()):   # the only read-back of the loop
+                run(max_iterations, 0)
+                break
+    return x, iterations, residual
 
 
 def _chk_align(x, lengths, weights=None):

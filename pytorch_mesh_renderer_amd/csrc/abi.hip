@@ -961,6 +961,48 @@ int mr_farthest_forward(const float *points, const int32_t *lengths, const int32
                                      (hipStream_t)stream);
 }
 
+inline bool bad_laplacian_dims(int B, int V, int C, int nnz) {
+  return B < 1 || B > 65535 || V < 1 || V >= (1 << 28) || C < 1 || C > 4 || nnz < 0 ||
+         (size_t)B * V * C >= ((size_t)1 << 36);
+}
+
+inline bool bad_lam(float lam) { return !(lam >= 0.0f && lam < INFINITY); }
+
+int mr_laplacian_apply(const float *x, const int32_t *nbr_offsets, const int32_t *nbr, int B, int V, int C, int nnz,
+                       float lam, float *y, void *stream) {
+  if (bad_laplacian_dims(B, V, C, nnz) || bad_lam(lam)) return MR_EINVAL;
+  if (!x || !y || !nbr_offsets || (nnz > 0 && !nbr)) return MR_EINVAL;
+  return mr::launch_laplacian_apply(x, nbr_offsets, nbr, B, V, C, nnz, lam, y, (hipStream_t)stream);
+}
+
+int mr_laplacian_solve_plan(int V, int C, int route, int *chosen_route, int *workgroup_size, int *vertices_per_lane,
+                            int *slices) {
+  if (bad_laplacian_dims(1, V, C, 0) || route < 0 || route > 2) return MR_EINVAL;
+  if (!chosen_route || !workgroup_size || !vertices_per_lane || !slices) return MR_EINVAL;
+  return mr::laplacian_solve_plan(V, C, route, chosen_route, workgroup_size, vertices_per_lane, slices) ? MR_OK
+                                                                                                        : MR_EINVAL;
+}
+
+size_t mr_laplacian_solve_workspace_bytes(int B, int V, int C) {
+  if (bad_laplacian_dims(B, V, C, 0)) return 0;
+  return mr::laplacian_solve_ws(B, V, C);
+}
+
+int mr_laplacian_solve(const float *b, const float *x0, const int32_t *nbr_offsets, const int32_t *nbr, int B, int V,
+                       int C, int nnz, float lam, double tol, int max_iterations, int route, int first_iteration,
+                       int iteration_count, int32_t *all_frozen, float *x, int32_t *iterations, float *residual,
+                       void *workspace, size_t workspace_bytes, void *stream) {
+  if (bad_laplacian_dims(B, V, C, nnz) || bad_lam(lam) || route < 0 || route > 2) return MR_EINVAL;
+  if (!(tol >= 0.0 && tol < (double)INFINITY) || max_iterations < 0 || max_iterations > 10000) return MR_EINVAL;
+  if (first_iteration < 0 || first_iteration > max_iterations || iteration_count < 0) return MR_EINVAL;
+  if (!b || !x || !iterations || !residual || !nbr_offsets || (nnz > 0 && !nbr)) return MR_EINVAL;
+  const int rc = check_ws(workspace, workspace_bytes, mr::laplacian_solve_ws(B, V, C));
+  if (rc != MR_OK) return rc;
+  return mr::launch_laplacian_solve(b, x0, nbr_offsets, nbr, B, V, C, nnz, lam, tol, max_iterations, route,
+                                    first_iteration, iteration_count, all_frozen, x, iterations, residual, workspace,
+                                    (hipStream_t)stream);
+}
+
 size_t mr_align_workspace_bytes(int B, int N) {
   if (bad_nearest_dims(B, N, 1)) return 0;
   return mr::align_ws(B, N);

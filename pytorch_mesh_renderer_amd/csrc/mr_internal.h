@@ -291,6 +291,15 @@ void farthest_plan(int B, int N, int K, int *route, int *workgroup, int *points_
 size_t farthest_ws(int B, int N, int K);
 int launch_farthest_forward(const float *points, const int32_t *lengths, const int32_t *start_idx, int B, int N, int K,
                             int route, int32_t *idx, float *radius, void *ws, hipStream_t s);
+// (I + lam L) apply and conjugate-gradient solve over mesh_topology()'s adjacency, mr_laplacian_* (mesh_solve.hip)
+bool laplacian_solve_plan(int V, int C, int route, int *chosen, int *workgroup, int *vertices_per_lane, int *slices);
+size_t laplacian_solve_ws(int B, int V, int C);
+int launch_laplacian_apply(const float *x, const int32_t *offsets, const int32_t *nbr, int B, int V, int C, int nnz,
+                           float lam, float *y, hipStream_t s);
+int launch_laplacian_solve(const float *rhs, const float *x0, const int32_t *offsets, const int32_t *nbr, int B, int V,
+                           int C, int nnz, float lam, double tol, int max_iterations, int route, int first_iteration,
+                           int iteration_count, int32_t *all_frozen, float *x, int32_t *iterations, float *residual,
+                           void *ws, hipStream_t s);
 // registration of matched point sets and ICP's per-round chain, mr_align_* (align.hip)
 size_t align_ws(int B, int N);
 int launch_align_solve(const float *x, const float *y, const int32_t *idx, int gather, const float *weights,

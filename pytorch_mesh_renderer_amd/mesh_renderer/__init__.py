@@ -8,6 +8,7 @@ from .texturing import (attribute_derivatives, render_textured, render_textured_
 from . import losses
 from . import regularizers
 from . import points
+from . import preconditioning
 from .graphs import capture_step, CapturedStep
 
 __version__ = '0.0.1'
