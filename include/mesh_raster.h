@@ -1053,6 +1053,37 @@ int mr_nearest_point_of_triangle_backward(const float *points, const float *vert
                                           const float *grad_images, const int32_t *usable, float *dpoints,
                                           float *dvertices, void *stream);
 
+/* ---- winding number: on which side of the mesh a point lies (no reference counterpart) ----
+ * The generalized winding number (Jacobson et al. 2013) of one shared topology around every query: per image b, for
+ * p = points[b,i] with i < lengths[b], over the triangles f with corners va, vb, vc = vertices[b, triangles[f]]
+ * ("Point-cloud losses"), in float32:
+ *   a = va - p, b = vb - p, c = vc - p
+ *   num = a . (b x c),   den = |a||b||c| + (a.b)|c| + (b.c)|a| + (c.a)|b|
+ *   t_f = 2 atan2(num, den) / (4 pi)   (|t_f| <= 0.5, atan2(0, 0) = 0),     w[b,i] = sum_f t_f
+ * 1 inside and 0 outside a closed mesh whose triangles are counter-clockwise seen from outside; in between for an
+ * open or folded one.  A triangle with an index outside [0, V) or with two equal indices is skipped; a geometrically
+ * degenerate triangle with three distinct indices is evaluated like any other.
+ * The sum is ORDER-FREE: every t_f is rounded to the nearest multiple of 2^-40 (ties to even), the rounded terms are
+ * added exactly in 64-bit integers and w = (float)(sum 2^-40), rounded once -- the same bits whatever the order of
+ * the triangles, the launch shape or the batch the image sat in (csrc/wn_fixed.h).  T > 2^24 is MR_EINVAL: the sum
+ * could leave the 64-bit range.  A padded query gets 0.  A query that met a num or a den that is not finite (a NaN or
+ * infinite point, a NaN vertex of a usable triangle, coordinates whose products overflow) gets NaN; other queries
+ * and other images are unaffected.  There is no backward: w is piecewise constant for a closed mesh.
+ *   points [B,N,3], vertices [B,V,3] f32;  triangles [T,3] i32;  lengths [B] i32 (device) or NULL = all N
+ *   w [B,N] f32 out
+ * mr_winding_number_plan: the launch shape, a pure host function, as mr_nearest_triangle_plan; with splits > 1 the
+ * runs of triangles meet through one 64-bit integer partial per (image, split, query), written with plain stores and
+ * added by a second launch: no atomics, stream order only, capturable.  The workspace holds the per-image triangle
+ * records (48 bytes each) and those partials; 16-byte aligned, needed by every call.
+ * 1 <= B <= 65535, 1 <= N, V <= 2^28, 1 <= T <= 2^24, B * N, B * V and B * T below 2^36; sizes outside are
+ * MR_EINVAL (queries return 0). */
+int mr_winding_number_plan(int B, int N, int T, int *splits, int *queries_per_lane, int *triangle_tile,
+                           int *workgroup_size);
+size_t mr_winding_number_workspace_bytes(int B, int N, int T);
+int mr_winding_number_forward(const float *points, const float *vertices, const int32_t *triangles,
+                              const int32_t *lengths, int B, int N, int V, int T, float *w, void *workspace,
+                              size_t workspace_bytes, void *stream);
+
 /* ---- clip-space transforms --------------------------------------------------------------
  * perspective(aspect, fov_y, near, far) . look_at(eye, center, up) per image, the product render() and
  * rasterize() apply to the vertices (src/common/camera_utils.py:45-139; src/mesh_renderer/render.py

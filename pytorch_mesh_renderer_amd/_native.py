@@ -445,6 +445,16 @@ def lib():
         except AttributeError as e:   # the registration entry points came without an ABI version bump
             raise NativeLibraryError("%s lacks the registration entry points (%s): rebuild it (make -C "
                                      "pytorch_mesh_renderer_amd/csrc)" % (LIB_PATH, e))
+        try:
+            L.mr_winding_number_plan.argtypes = [ci] * 3 + [vp] * 4
+            L.mr_winding_number_plan.restype = ci
+            L.mr_winding_number_workspace_bytes.argtypes = [ci] * 3
+            L.mr_winding_number_workspace_bytes.restype = sz
+            L.mr_winding_number_forward.argtypes = [vp] * 4 + [ci] * 4 + [vp, vp, sz, vp]
+            L.mr_winding_number_forward.restype = ci
+        except AttributeError as e:   # the winding-number entry points came without an ABI version bump
+            raise NativeLibraryError("%s lacks the winding-number entry points (%s): rebuild it (make -C "
+                                     "pytorch_mesh_renderer_amd/csrc)" % (LIB_PATH, e))
         _lib = L
     return _lib
 
@@ -1663,6 +1673,34 @@ def nearest_triangle_backward(points, vertices, triangles, lengths, face, bary, 
                                             _ptr(dpoints), _ptr(dvertices), _stream(dev))
     _check(rc, "mr_nearest_triangle_backward")
     return dpoints, dvertices
+
+
+def winding_number_plan(B, N, T):
+    """The launch shape mr_winding_number_forward takes for B images of N queries against T triangles, a pure host
+    function: {"splits", "queries_per_lane", "triangle_tile", "workgroup_size"} (include/mesh_raster.h).  T above
+    2^24 is refused: the fixed-point sum could leave the 64-bit range."""
+    return _plan("winding_number_plan", (B, N, T),
+                 ("splits", "queries_per_lane", "triangle_tile", "workgroup_size"),
+                 "1..65535 images of 1..2^28 points and 1..2^24 triangles")
+
+
+def winding_number_forward(points, vertices, triangles, lengths=None):
+    """points [B,N,3], vertices [B,V,3] f32, triangles [T,3] i32, lengths [B] i32 or None (device) -> w [B,N] f32, the
+    generalized winding number of the mesh around every valid query (0 in padded rows): mr_winding_number_forward."""
+    B, N, V, T = _chk_point_mesh(points, vertices, triangles, lengths)
+    if T > 1 << 24:
+        raise ValueError("the winding number takes at most 2^24 triangles, got %d" % T)
+    dev = _require_device(points, vertices, triangles, *([lengths] if lengths is not None else []))
+    L = lib()
+    points, vertices, triangles = points.contiguous(), vertices.contiguous(), triangles.contiguous()
+    lengths = lengths.contiguous() if lengths is not None else None
+    w = torch.empty(B, N, dtype=_F32, device=dev)
+    with torch.cuda.device(dev):
+        ws, have = _workspace(dev, L.mr_winding_number_workspace_bytes(B, N, T))
+        rc = L.mr_winding_number_forward(_ptr(points), _ptr(vertices), _ptr(triangles), _ptr(lengths), B, N, V, T,
+                                         _ptr(w), _ptr(ws), have, _stream(dev))
+    _check(rc, "mr_winding_number_forward")
+    return w
 
 
 def nearest_point_of_triangle_plan(B, N, T):

@@ -1129,6 +1129,36 @@ int mr_nearest_triangle_backward(const float *points, const float *vertices, con
                                               (hipStream_t)stream);
 }
 
+// the fixed-point sum of 2^24 terms of at most half a turn each is the last that cannot leave the 64-bit range
+inline bool bad_winding_number_dims(int B, int N, int T) {
+  return bad_nearest_dims(B, N, T) || T > mr::winding_number_max_triangles();
+}
+
+int mr_winding_number_plan(int B, int N, int T, int *splits, int *queries_per_lane, int *triangle_tile,
+                           int *workgroup_size) {
+  if (bad_winding_number_dims(B, N, T) || !splits || !queries_per_lane || !triangle_tile || !workgroup_size)
+    return MR_EINVAL;
+  mr::winding_number_plan(B, N, T, splits, queries_per_lane, triangle_tile, workgroup_size);
+  return MR_OK;
+}
+
+size_t mr_winding_number_workspace_bytes(int B, int N, int T) {
+  if (bad_winding_number_dims(B, N, T)) return 0;
+  return mr::winding_number_ws(B, N, T);
+}
+
+int mr_winding_number_forward(const float *points, const float *vertices, const int32_t *triangles,
+                              const int32_t *lengths, int B, int N, int V, int T, float *w, void *workspace,
+                              size_t workspace_bytes, void *stream) {
+  if (bad_nearest_triangle_dims(B, N, V, T) || bad_winding_number_dims(B, N, T)) return MR_EINVAL;
+  if (!points || !vertices || !triangles || !w) return MR_EINVAL;
+  const int rc = check_ws(workspace, workspace_bytes, mr::winding_number_ws(B, N, T));
+  if (rc != MR_OK) return rc;
+  if (misaligned(workspace, 16)) return MR_EINVAL;   // the records are read as 16-byte words
+  return mr::launch_winding_number_forward(points, vertices, triangles, lengths, B, N, V, T, w, workspace,
+                                           (hipStream_t)stream);
+}
+
 int mr_nearest_point_of_triangle_plan(int B, int N, int T, int *splits, int *points_per_step, int *point_tile,
                                       int *workgroup_size) {
   if (bad_nearest_dims(B, N, T) || !splits || !points_per_step || !point_tile || !workgroup_size) return MR_EINVAL;

@@ -324,6 +324,14 @@ int launch_nearest_triangle_backward(const float *points, const float *vertices,
                                      const float *bary, const int32_t *order, const int32_t *offsets,
                                      const float *grad_points, const float *grad_images, float *dpoints,
                                      float *dvertices, hipStream_t s);
+// winding number, mr_winding_number_* (nearest.hip; the fixed-point sum: wn_fixed.h)
+void winding_number_plan(int B, int N, int T, int *splits, int *queries_per_lane, int *triangle_tile, int *workgroup);
+int winding_number_max_triangles();
+size_t winding_number_ws(int B, int N, int T);
+int launch_winding_number_forward(const float *points, const float *vertices, const int32_t *triangles,
+                                  const int32_t *lengths, int B, int N, int V, int T, float *w, void *ws,
+                                  hipStream_t s);
+
 // triangle to nearest point, mr_nearest_point_of_triangle_* (nearest.hip)
 void nearest_point_of_triangle_plan(int B, int N, int T, int *splits, int *points_per_step, int *point_tile,
                                     int *workgroup);

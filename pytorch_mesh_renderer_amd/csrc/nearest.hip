@@ -2,7 +2,9 @@
 // (mr_nearest_forward / _backward; semantics: INTEGRATION.md, "Point-cloud losses"), and further down the same search
 // from points to the triangles of a mesh (mr_nearest_triangle_forward / _backward: "point to triangle") and, last,
 // from the triangles to the points (mr_nearest_point_of_triangle_forward / _backward: "triangle to point"), and the
-// K-neighbour form of the point search (mr_knn_forward / _backward: "K nearest neighbours").
+// K-neighbour form of the point search (mr_knn_forward / _backward: "K nearest neighbours"), and the winding number
+// of the mesh around every point (mr_winding_number_forward: "winding number"): the same all-pairs loop with '+' where
+// the searches have 'min'.
 //
 // Per image b, for every query x_i (i < x_lengths[b]) over the targets y_j (j < y_lengths[b]):
 //   sqdist_i = min_j (x_i - y_j).(x_i - y_j),   idx_i = the lowest j that attains it
@@ -21,6 +23,7 @@
 #include <math.h>
 
 #include "mr_internal.h"
+#include "wn_fixed.h"
 
 namespace mr {
 namespace {
@@ -1058,6 +1061,156 @@ __global__ __launch_bounds__(kThreads) void k_knn_backward(
   });
 }
 
+// ---- winding number ---------------------------------------------------------------------------------------------
+// mr_winding_number_forward: per image, for every query p the generalized winding number of the mesh around it
+// (Jacobson et al. 2013; INTEGRATION.md, "Point-cloud losses"): the sum over the usable triangles of the signed solid
+// angle seen from p over 4 pi, with a = va - p, b = vb - p, c = vc - p (Van Oosterom and Strackee)
+//   num = a . (b x c),  den = |a||b||c| + (a.b)|c| + (b.c)|a| + (c.a)|b|,  t = 2 atan2(num, den) / (4 pi),  |t| <= 0.5.
+// It is the searches' all-pairs loop with '+' where they have 'min', on the searches' frame: k_wn_setup gathers every
+// image's triangles into 48-byte records (the three corners; the spare lane of the first word says whether the
+// triangle is usable: every index in [0, V) and no two equal), k_wn_sum stages 128 of them in LDS, every lane reads
+// the same record as three 16-byte reads (a ds_read_b128 and two ds_read_b96, the spare lanes of the last two words
+// being unused: one address for the wavefront, a broadcast) and keeps one query, or two in packed fp32, with their
+// sums in registers.  The sum is in 64-bit fixed point (wn_fixed.h), so it is the same number whatever the order and the
+// launch shape: with splits > 1 every (image, split, query) writes its integer partial with a plain store and
+// k_wn_merge adds them -- no atomics, no flags, stream order alone.  A query that met a non-finite num or den (a NaN
+// or infinite point, a NaN vertex of a usable triangle, an overflow) is poisoned: NaN out, kWnPoisoned between the
+// splits.  wn_terms is compiled without contraction and with explicit fused multiply-adds, as tri_candidates is, and
+// the square roots and the arctangent are taken half by half, so the scalar and the packed instantiation round alike.
+constexpr int kWnRecWords = 3;         // 16-byte words per record: a.xyz, usable | b.xyz, - | c.xyz, -
+constexpr float kInvTwoPi = 0.15915494309189535f;
+
+__device__ __forceinline__ float root_of(float v) { return __builtin_amdgcn_sqrtf(v); }   // v_sqrt_f32: 1 ulp
+__device__ __forceinline__ F2 root_of(F2 v) { return F2{root_of(v.x), root_of(v.y)}; }
+// atan2(num, den) / (2 pi), kept within the +-0.5 the fixed-point format counts on (float(pi) is above pi)
+__device__ __forceinline__ float turn_of(float num, float den) {
+  return fminf(fmaxf(atan2f(num, den) * kInvTwoPi, -0.5f), 0.5f);
+}
+__device__ __forceinline__ F2 turn_of(F2 num, F2 den) { return F2{turn_of(num.x, den.x), turn_of(num.y, den.y)}; }
+
+__device__ __forceinline__ float where(bool keep, float v) { return keep ? v : 0.0f; }
+__device__ __forceinline__ F2 where(bool keep, F2 v) { return F2{where(keep, v.x), where(keep, v.y)}; }
+
+// num and den of one triangle (its record's three words) for one (float) or two (F2) queries.
+template <typename F>
+__device__ __forceinline__ void wn_terms(F px, F py, F pz, float4 r0, float4 r1, float4 r2, F &num, F &den) {
+#pragma clang fp contract(off)   // every fused multiply-add below is spelled: both instantiations round alike
+  const F ax = (F)r0.x - px, ay = (F)r0.y - py, az = (F)r0.z - pz;
+  const F bx = (F)r1.x - px, by = (F)r1.y - py, bz = (F)r1.z - pz;
+  const F cx = (F)r2.x - px, cy = (F)r2.y - py, cz = (F)r2.z - pz;
+  const F nx = fma_of(by, cz, -(bz * cy)), ny = fma_of(bz, cx, -(bx * cz)), nz = fma_of(bx, cy, -(by * cx));
+  num = fma_of(az, nz, fma_of(ay, ny, ax * nx));
+  const F la = root_of(fma_of(az, az, fma_of(ay, ay, ax * ax)));
+  const F lb = root_of(fma_of(bz, bz, fma_of(by, by, bx * bx)));
+  const F lc = root_of(fma_of(cz, cz, fma_of(cy, cy, cx * cx)));
+  const F ab = fma_of(az, bz, fma_of(ay, by, ax * bx));
+  const F bc = fma_of(bz, cz, fma_of(by, cy, bx * cx));
+  const F ca = fma_of(cz, az, fma_of(cy, ay, cx * ax));
+  den = fma_of(ca, lb, fma_of(bc, la, fma_of(ab, lc, la * lb * lc)));
+}
+
+// grid (ceil(T / kThreads), B): records [B, T, kWnRecWords] of 16-byte words
+__global__ __launch_bounds__(kThreads) void k_wn_setup(const V3 *__restrict__ vertices,
+                                                       const int32_t *__restrict__ triangles, int V, int T,
+                                                       float4 *__restrict__ records) {
+  const int b = (int)blockIdx.y, t = (int)blockIdx.x * kThreads + (int)threadIdx.x;
+  if (t >= T) return;
+  float4 *out = records + ((size_t)b * T + t) * kWnRecWords;
+  int ia, ib, ic;
+  if (!usable_triangle(triangles, t, V, ia, ib, ic) || ia == ib || ib == ic || ic == ia) {
+    out[0] = out[1] = out[2] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);   // skipped: contributes nothing
+    return;
+  }
+  const V3 *vb = vertices + (size_t)b * V;
+  const V3 a = vb[ia], p = vb[ib], c = vb[ic];
+  out[0] = make_float4(a.x, a.y, a.z, 1.0f);
+  out[1] = make_float4(p.x, p.y, p.z, 0.0f);
+  out[2] = make_float4(c.x, c.y, c.z, 0.0f);
+}
+
+// grid (query blocks, splits, B).  partials != null (splits > 1): one 64-bit partial per (image, split, query) for
+// k_wn_merge, 0 for a padded query; partials == null: w itself.
+template <typename F>
+__global__ __launch_bounds__(kThreads) void k_wn_sum(const float *__restrict__ points,
+                                                     const float4 *__restrict__ records,
+                                                     const int32_t *__restrict__ lengths, int N, int T, int chunk,
+                                                     float *__restrict__ w, long long *__restrict__ partials) {
+  constexpr int Q = (int)(sizeof(F) / sizeof(float));
+  __shared__ float4 tile[kTriTile * kWnRecWords];
+  const int b = (int)blockIdx.z, split = (int)blockIdx.y;
+  const int nv = valid_count(lengths, b, N);
+  const float4 *rb = records + (size_t)b * T * kWnRecWords;
+  const Range run = split_range(split, chunk, T);
+  const int i0 = (int)blockIdx.x * (kThreads * Q) + (int)threadIdx.x;
+
+  float qx[Q], qy[Q], qz[Q];
+  load_queries<Q>(points + (size_t)b * N * 3, i0, nv, qx, qy, qz);
+  F px, py, pz;
+  if constexpr (Q == 2) {
+    px = F{qx[0], qx[1]};
+    py = F{qy[0], qy[1]};
+    pz = F{qz[0], qz[1]};
+  } else {
+    px = qx[0];
+    py = qy[0];
+    pz = qz[0];
+  }
+  long long sum[Q];
+#pragma unroll
+  for (int q = 0; q < Q; ++q) sum[q] = 0;
+  F bad = (F)0.0f;   // 0, or NaN once a num or a den was not finite
+
+  for (int t0 = run.j0; t0 < run.j1; t0 += kTriTile) {
+    const int count = min(kTriTile, run.j1 - t0);
+    __syncthreads();
+    for (int f = (int)threadIdx.x; f < count * kWnRecWords; f += kThreads)
+      tile[f] = rb[(size_t)t0 * kWnRecWords + f];
+    __syncthreads();
+    for (int j = 0; j < count; ++j) {
+      const float4 *r = &tile[j * kWnRecWords];   // one address for the wavefront
+      const float4 r0 = r[0];
+      F num, den;
+      wn_terms<F>(px, py, pz, r0, r[1], r[2], num, den);
+      // a skipped triangle (the same on every lane) is atan2(0, 0) = 0: selects, no branch between the LDS reads
+      num = where(r0.w != 0.0f, num), den = where(r0.w != 0.0f, den);
+      bad = fma_of(num, (F)0.0f, fma_of(den, (F)0.0f, bad));   // x * 0 is NaN for an infinite or NaN x
+      const F turn = turn_of(num, den);
+#pragma unroll
+      for (int q = 0; q < Q; ++q) sum[q] += wn_to_fixed(part_of(turn, q));
+    }
+  }
+
+#pragma unroll
+  for (int q = 0; q < Q; ++q) {
+    const int i = i0 + q * kThreads;
+    if (i >= N) continue;
+    const bool valid = i < nv, poisoned = part_of(bad, q) != 0.0f;
+    if (partials)
+      partials[((size_t)b * gridDim.y + split) * N + i] = !valid ? 0 : (poisoned ? kWnPoisoned : sum[q]);
+    else
+      w[(size_t)b * N + i] = !valid ? 0.0f : (poisoned ? __int_as_float(0x7fc00000) : wn_to_float(sum[q]));
+  }
+}
+
+// The sum of a query's partials over the splits -> w; NaN when one of them is poisoned, 0 for a padded query.
+// grid (ceil(N / kThreads), B)
+__global__ __launch_bounds__(kThreads) void k_wn_merge(const long long *__restrict__ partials, int splits,
+                                                       const int32_t *__restrict__ lengths, int N,
+                                                       float *__restrict__ w) {
+  const int b = (int)blockIdx.y;
+  const int i = (int)blockIdx.x * kThreads + (int)threadIdx.x;
+  if (i >= N) return;
+  long long sum = 0;
+  bool poisoned = false;
+  for (int s = 0; s < splits; ++s) {
+    const long long part = partials[((size_t)b * splits + s) * N + i];
+    poisoned |= part == kWnPoisoned;
+    sum += poisoned ? 0 : part;
+  }
+  const bool valid = i < valid_count(lengths, b, N);
+  w[(size_t)b * N + i] = !valid ? 0.0f : (poisoned ? __int_as_float(0x7fc00000) : wn_to_float(sum));
+}
+
 // ---- launches ---------------------------------------------------------------------------------------------------
 // One kernel, workgroups of kThreads, on stream s -> MR_OK or MR_ELAUNCH.
 template <typename Kernel, typename... Args>
@@ -1234,6 +1387,40 @@ int launch_nearest_point_of_triangle_backward(const float *points, const float *
     rc = launch(k_nt_backward_vertices<true>, groups_grid(V, B), s, (const V3 *)points, (const V3 *)vertices, triangles,
                 lengths, N, V, T, index, (const V3 *)bary, corner_order, corner_offsets, grad_triangles, grad_images,
                 usable, (V3 *)dvertices);
+  return rc;
+}
+
+// the winding number starts from the triangle search's shape: the same tile, one packed pair of queries a lane
+inline Plan wn_plan_of(int B, int N, int T) { return plan_of(B, N, T, kTriTile, kTriWideQueries); }
+// the triangle records | the splits' 64-bit partials, one per query (splits > 1)
+inline Layout wn_layout(const Plan &p, int B, int N, int T) {
+  return layout_of(p, B, align_up((size_t)B * T * kWnRecWords * sizeof(float4), 256), (size_t)N, 0);
+}
+
+void winding_number_plan(int B, int N, int T, int *splits, int *queries_per_lane, int *triangle_tile, int *workgroup) {
+  const Plan p = wn_plan_of(B, N, T);
+  *splits = p.splits;
+  *queries_per_lane = p.queries_per_lane;
+  *triangle_tile = kTriTile;
+  *workgroup = kThreads;
+}
+
+int winding_number_max_triangles() { return kWnMaxTriangles; }
+
+size_t winding_number_ws(int B, int N, int T) { return wn_layout(wn_plan_of(B, N, T), B, N, T).bytes; }
+
+int launch_winding_number_forward(const float *points, const float *vertices, const int32_t *triangles,
+                                  const int32_t *lengths, int B, int N, int V, int T, float *w, void *ws,
+                                  hipStream_t s) {
+  const Plan p = wn_plan_of(B, N, T);
+  const Workspace space = carve(ws, p, wn_layout(p, B, N, T), false);
+  long long *partials = (long long *)space.keys;   // null without a split
+  int rc = launch(k_wn_setup, rows_grid(T, B), s, (const V3 *)vertices, triangles, V, T, space.records);
+  if (rc != MR_OK) return rc;
+  const auto sum = p.queries_per_lane == kTriWideQueries ? k_wn_sum<F2> : k_wn_sum<float>;
+  rc = launch(sum, search_grid(p, B), s, points, (const float4 *)space.records, lengths, N, T, p.chunk, w, partials);
+  if (rc == MR_OK && partials)
+    rc = launch(k_wn_merge, rows_grid(N, B), s, (const long long *)partials, p.splits, lengths, N, w);
   return rc;
 }
 

@@ -10,6 +10,9 @@ Distances are always computed as (x - y).(x - y), never as |x|^2 + |y|^2 - 2 x.y
 point_mesh_distance measure to the mesh's surface itself -- the nearest closed triangle -- with kernels of the same
 file and the same split between the HIP and the torch path; triangle_nearest_points and mesh_point_distance are the
 other direction, every triangle against its nearest point, and point_mesh_face_distance is the sum of the two means.
+winding_number says on which side of the mesh a point lies -- the generalized winding number, an order-free fixed-point
+sum over all triangles with kernels of the same file -- inside_mesh thresholds it, and signed_distance puts its sign
+on nearest_triangles' distance.
 knn_points is the K-neighbour form of nearest_points (a sorted list of K keys per query in registers, same file, same
 split between the two paths), knn_gather reads values at its indices, and estimate_point_normals is its first
 consumer: the normals of a scan from the covariance of every point's neighbourhood.  sample_farthest_points thins a
@@ -859,6 +862,99 @@ def point_mesh_face_distance(points, vertices, triangles, lengths=None):
     a mesh under PyTorch3D's name, each a mean of its own (over the valid points, over the usable triangles)."""
     return (point_mesh_distance(points, vertices, triangles, lengths)
             + mesh_point_distance(points, vertices, triangles, lengths))
+
+
+# ---- inside or outside: the winding number and the signed distance ------------------------------------------------------
+
+_WN_FRAC_BITS = 40          # csrc/wn_fixed.h: every term is rounded to a multiple of 2^-40 and summed in int64
+_WN_MAX_TRIANGLES = 1 << 24
+
+
+def _winding_number_torch(points, v, tris, lengths):
+    """winding_number as a torch expression on the device and in the dtype of points [B,N,3] / v [B,V,3], chunked
+    over the queries: the same definition as the kernels', the fixed-point sum included (the terms themselves are
+    rounded by torch's own arithmetic, so the two routes agree within the rounding bound, not bit for bit)."""
+    B, N, _ = points.shape
+    V, T = v.shape[1], tris.shape[0]
+    dev = points.device
+    n_valid = lengths.long() if lengths is not None else torch.full((B,), N, dtype=torch.int64, device=dev)
+    with torch.no_grad():
+        points, v = points.detach(), v.detach()
+        usable = (((tris >= 0) & (tris < V)).all(dim=1) & (tris[:, 0] != tris[:, 1]) & (tris[:, 1] != tris[:, 2])
+                  & (tris[:, 2] != tris[:, 0]))
+        safe = tris.clamp(0, V - 1)
+        va, vb, vc = (v.index_select(1, safe[:, k])[:, None] for k in range(3))          # [B,1,T,3]
+        rows = max(1, _CHUNK_BYTES // max(1, B * T * 16 * points.element_size()))
+        out = []
+        for start in range(0, N, rows):
+            p = points[:, start:start + rows, None, :]
+            a, b, c = va - p, vb - p, vc - p
+            la, lb, lc = (torch.sqrt((x * x).sum(-1)) for x in (a, b, c))
+            num = (a * torch.cross(b, c, dim=-1)).sum(-1)
+            den = la * lb * lc + (a * b).sum(-1) * lc + (b * c).sum(-1) * la + (c * a).sum(-1) * lb
+            finite = torch.isfinite(num) & torch.isfinite(den)
+            turn = 2.0 * torch.atan2(num, den) / (4.0 * torch.pi)
+            counted = usable[None, None, :] & finite
+            fixed = torch.round(torch.where(counted, turn, torch.zeros_like(turn)).double() * 2.0 ** _WN_FRAC_BITS)
+            w = fixed.to(torch.int64).sum(-1).to(points.dtype) * 2.0 ** -_WN_FRAC_BITS
+            poisoned = (usable[None, None, :] & ~finite).any(-1)
+            out.append(torch.where(poisoned, torch.full_like(w, float("nan")), w))
+        w = torch.cat(out, dim=1)
+        padded = torch.arange(N, device=dev)[None, :] >= n_valid[:, None]
+        return torch.where(padded, torch.zeros_like(w), w)
+
+
+def winding_number(points, vertices, triangles, lengths=None):
+    """points [B,N,3], vertices [B,V,3] (or [N,3], [V,3]: one image, the result without the batch axis), triangles
+    [T,3] of any integer dtype (one topology for the batch, at most 2^24 triangles) -> w [B,N]: the generalized
+    winding number (Jacobson et al. 2013) of the mesh around every point, the sum of the signed solid angles of all
+    triangles seen from the point over 4 pi.  With a = va - p, b = vb - p, c = vc - p per triangle:
+        num = a . (b x c),   den = |a||b||c| + (a.b)|c| + (b.c)|a| + (c.a)|b|,   t = 2 atan2(num, den) / (4 pi)
+    For a closed mesh whose triangles are counter-clockwise seen from outside (shapes.cube) w is 1 inside and 0
+    outside; for an open or folded mesh it degrades gracefully (0.96 at the centre of shapes.sphere, which is not
+    watertight).  A triangle with an index outside [0, V) or with two equal indices is skipped.
+
+    The sum is order-free: every term is rounded to the nearest multiple of 2^-40 and the rounded terms are added
+    exactly as 64-bit integers, so on a HIP device (csrc/nearest.hip, k_wn_*) w is the same bit for bit whatever the
+    order of the triangles, the launch shape or the batch an image sits in.  Host tensors and tensors that are not
+    float32 take the torch expression of the same definition.
+
+    lengths: an optional integer [B] tensor on the points' device for padded clouds; a padded row gets 0.  A point
+    that meets a num or den that is not finite (a NaN or infinite point, a NaN vertex of a counted triangle) gets
+    NaN; other points and other images are unaffected.
+
+    NO GRADIENT: the result never requires grad.  For a closed mesh w is piecewise constant in the points and the
+    vertices, so its gradient is zero almost everywhere and useless as a fitting signal; signed_distance is the
+    differentiable companion."""
+    p, v, tris, lengths, single = _point_mesh_arguments(points, vertices, triangles, lengths)
+    if tris.shape[0] > _WN_MAX_TRIANGLES:
+        raise ValueError("winding_number takes at most 2^24 triangles (the fixed-point sum's range), got %d"
+                         % tris.shape[0])
+    if _on_hip_path(p):
+        w = _native.winding_number_forward(p.detach(), v.detach(), _device_triangles(tris, v.shape[1]), lengths)
+    else:
+        w = _winding_number_torch(p, v, tris, lengths)
+    return w[0] if single else w
+
+
+def inside_mesh(points, vertices, triangles, lengths=None, threshold=0.5):
+    """winding_number(...) >= threshold -> bool [B,N]: which points the mesh encloses.  NaN and padded rows give
+    False."""
+    return winding_number(points, vertices, triangles, lengths) >= threshold
+
+
+def signed_distance(points, vertices, triangles, lengths=None, threshold=0.5):
+    """The distance of every point to the mesh's surface with the sign of inside_mesh -> [B,N]: s sqrt(sqdist) with
+    sqdist from nearest_triangles and s = -1 where winding_number >= threshold, +1 elsewhere (NaN winding numbers
+    included).  Differentiable in points and vertices through nearest_triangles' backward; s is a constant in the
+    gradient, and the gradient is 0, not NaN, where the distance is 0.  A padded row, and a point without a nearest
+    triangle, get 0."""
+    sqdist = nearest_triangles(points, vertices, triangles, lengths)[0]
+    inside = inside_mesh(points, vertices, triangles, lengths, threshold)
+    nonzero = sqdist > 0   # the _safe_norm pattern of regularizers.py: sqrt never sees the 0 whose slope is infinite
+    distance = torch.where(nonzero, torch.sqrt(torch.where(nonzero, sqdist, torch.ones_like(sqdist))),
+                           torch.zeros_like(sqdist))
+    return torch.where(inside, -distance, distance)
 
 
 # ---- registration: the similarity transform between matched points, and ICP ---------------------------------------------
