@@ -934,10 +934,13 @@ int mr_laplacian_solve(const float *b, const float *x0, const int32_t *nbr_offse
  *   and no gathered cloud is ever formed.  weights [B,N] f32 or NULL;  sqdist [B,N] f32 or NULL: a row is kept only
  *   while sqdist <= max_sqdist;  lengths [B] i32 or NULL, clamped by the kernels; padded rows influence nothing.
  *   R [B,3,3], T [B,3], s [B] f32 out;  rmse [B] f32 out or NULL.
- * Two launches: eighteen float64 moments about a pivot (row 0 of x and of y) summed per workgroup over fixed chunks of
- * 1024 rows into the workspace (B * ceil(N / 1024) * 144 bytes rounded up to 256) and then in a fixed order, no
- * atomics -- the result of an image does not depend on the padding or the other images of its batch; then one lane per
- * image in float64: a cyclic one-sided Jacobi SVD with a fixed sweep bound, rounded to float32 once at the end.
+ * Two launches: eighteen float64 moments summed per workgroup over fixed chunks of 1024 rows, each chunk about a
+ * reference point of its own -- its first kept row of positive weight and that row's match, never a row that is not
+ * counted -- and left in the workspace (B * ceil(N / 1024) * 144 bytes rounded up to 256) as the chunk's W, means and
+ * moments centred on those means; the chunks are merged in a fixed order, no atomics -- the result of an image does not
+ * depend on the padding or the other images of its batch, nor on the coordinates of a row with weight 0 (finite ones)
+ * or of a dropped or padded row (any); then one lane per image in float64: a cyclic one-sided Jacobi SVD with a fixed
+ * sweep bound, rounded to float32 once at the end.
  * ICP's bookkeeping, all three given or all NULL (rmse is then required): converged [B] i32, iterations [B] i32,
  * prev_rmse [B] f64 (8-byte aligned), initialised by mr_align_icp_init.  An image with converged != 0 is left untouched,
  * bit for bit.  Otherwise iterations += 1 and, with the float64 rmse before rounding: converged = 1 when rmse == 0 or,

@@ -5,15 +5,18 @@
 // (E = I with allow_reflection), s = tr(S E) / var(x), T = ym - s xm R.
 //
 //   k_align_moments  grid (chunks, B): a workgroup sums eighteen float64 moments over ITS kMomentRows rows of an image
-//                    -- W, sum w x, sum w y, sum w x y^T, sum w |x|^2, sum w |y|^2, of x - px and y - py about a pivot
-//                    (row 0 of x and of y where finite) so that a cloud far from the origin loses nothing to
-//                    cancellation -- and leaves one partial.  y is read row by row or through an idx plane; a row
-//                    with idx < 0 (or >= M when gathering) or with sqdist above the cut-off is dropped.
-//   k_align_solve    grid (B): adds an image's partials in a fixed order (eight interleaved groups of chunks, then
-//                    the groups in ascending order), then ONE lane does the rest in float64: centring, a one-sided
-//                    cyclic Jacobi SVD of the 3x3 covariance with a fixed sweep bound, the determinant correction,
-//                    scale, translation and the residual in closed form, rounds once to float32, and keeps ICP's
-//                    convergence bookkeeping.  A converged image's state is left untouched.
+//                    -- W, sum w x, sum w y, sum w x y^T, sum w |x|^2, sum w |y|^2, of x and y minus a reference
+//                    point, the chunk's own first kept row of positive weight and its match, so that a cloud far from
+//                    the origin loses nothing to cancellation and a row that is not counted (weight 0, dropped,
+//                    padded) influences nothing -- and leaves one partial: W, the chunk's means, and the moments
+//                    centred on them.  y is read row by row or through an idx plane; a row with idx < 0 (or >= M when
+//                    gathering) or with sqdist above the cut-off is dropped.
+//   k_align_solve    grid (B): merges an image's partials in a fixed order (eight interleaved groups of chunks, then
+//                    the groups in ascending order; the means first, then the moments moved onto them), then ONE lane
+//                    does the rest in float64: a one-sided cyclic Jacobi SVD of the 3x3 covariance with a fixed sweep
+//                    bound, the determinant correction, scale, translation and the residual in closed form, rounds
+//                    once to float32, and keeps ICP's convergence bookkeeping.  A converged image's state is left
+//                    untouched.
 //   k_align_apply    Xt = s X R + T, padded rows 0.
 //   k_align_closest  the closest point sum bary corner of mr_nearest_triangle_forward's (face, bary).
 //   k_align_init     ICP's state before the first round (a kernel, not a memset: see zero_async).
@@ -33,8 +36,12 @@ constexpr int kMomentWaves = kMomentThreads / kWave;
 constexpr int kRowsPerThread = 4;
 constexpr int kMomentRows = kMomentThreads * kRowsPerThread;   // rows of a chunk
 constexpr int kMoments = 18;
+constexpr int kMeanSums = 7;       // W and the six first moments
+constexpr int kCentredSums = 11;   // the nine cross moments and the two variances
+constexpr int kNoRow = 0x7fffffff;
 constexpr int kSolveThreads = 256;
-constexpr int kSolveGroups = kSolveThreads / 32;   // 8 groups of 32 lanes, lane m < 18 of a group owns moment m
+constexpr int kSolveWaves = kSolveThreads / kWave;
+constexpr int kSolveGroups = kSolveThreads / 32;   // 8 groups of 32 lanes, lane m of a group owns sum m
 constexpr int kJacobiSweeps = 16;
 constexpr double kRankTolerance = 1e-13;   // a singular value below this multiple of the largest counts as 0
 
@@ -44,52 +51,94 @@ __device__ __forceinline__ int valid_rows(const int32_t *__restrict__ lengths, i
   return lengths ? min(max(lengths[b], 0), N) : N;
 }
 
-__device__ __forceinline__ double pivot_of(float v) { return fabsf(v) < INFINITY ? (double)v : 0.0; }   // 0 for NaN
-
-// grid (chunks, B).  partials [B][chunks][18].
+// grid (chunks, B).  partials [B][chunks][18]: W, the chunk's weighted means of x and of y (3 + 3; 0 where W = 0), and
+// eleven moments CENTRED on those means: sum w (x - mx)(y - my)^T (9), sum w |x - mx|^2, sum w |y - my|^2.
 __global__ __launch_bounds__(kMomentThreads) void k_align_moments(
     const float *__restrict__ x, const float *__restrict__ y, const int32_t *__restrict__ idx, int gather,
     const float *__restrict__ weights, const float *__restrict__ sqdist, float max_sqdist,
     const int32_t *__restrict__ lengths, const int32_t *__restrict__ converged, int N, int M,
     double *__restrict__ partials) {
   __shared__ double lds[kMomentWaves][kMoments];
+  __shared__ double sums[kMoments];
+  __shared__ int first_of_wave[kMomentWaves];
+  __shared__ float reference[6];
   const int b = (int)blockIdx.y, chunk = (int)blockIdx.x, tid = (int)threadIdx.x;
   if (converged && converged[b]) return;   // (the whole workgroup) a frozen image: nobody reads its partials
   const int nv = valid_rows(lengths, b, N);
   const float *xb = x + (size_t)b * N * 3;
   const float *yb = y + (size_t)b * (gather ? M : N) * 3;
-  const double px = pivot_of(xb[0]), py = pivot_of(xb[1]), pz = pivot_of(xb[2]);
-  const double qx = pivot_of(yb[0]), qy = pivot_of(yb[1]), qz = pivot_of(yb[2]);
+  const int lane = tid & (kWave - 1), wave = tid >> 6;
+
+  // a thread's four rows, loaded once: a dropped row has weight 0 and coordinates 0
+  float px[kRowsPerThread][3], py[kRowsPerThread][3];
+  double w[kRowsPerThread];
+  int first = kNoRow;   // the lowest kept row of positive weight
+#pragma unroll
+  for (int j = 0; j < kRowsPerThread; ++j) {
+    const int i = chunk * kMomentRows + j * kMomentThreads + tid;   // (chunks * kMomentRows < 2^31: N <= 2^28)
+    bool kept = i < nv;
+    const size_t at = (size_t)b * N + (kept ? i : 0);
+    int row = i;
+    if (kept && idx) {
+      const int k = idx[at];
+      if (k < 0 || (gather && k >= M)) kept = false;
+      else if (gather) row = k;
+    }
+    if (kept && sqdist && !(sqdist[at] <= max_sqdist)) kept = false;
+    w[j] = 0.0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) px[j][k] = 0.0f, py[j][k] = 0.0f;
+    if (kept) {
+      w[j] = weights ? (double)weights[at] : 1.0;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) px[j][k] = xb[3 * (size_t)i + k], py[j][k] = yb[3 * (size_t)row + k];
+      if (w[j] > 0.0 && first == kNoRow) first = j * kMomentThreads + tid;
+    }
+  }
+  // the chunk's reference point: its first kept row of positive weight (0 without one), found by a minimum, handed
+  // round through LDS by the thread that holds it.  A row that is not counted never becomes the reference.
+  int lowest = first;
+#pragma unroll
+  for (int step = kWave / 2; step > 0; step >>= 1) lowest = min(lowest, __shfl_xor(lowest, step, kWave));
+  if (lane == 0) first_of_wave[wave] = lowest;
+  __syncthreads();
+  lowest = first_of_wave[0];
+#pragma unroll
+  for (int wv = 1; wv < kMomentWaves; ++wv) lowest = min(lowest, first_of_wave[wv]);
+  if (lowest != kNoRow && (lowest & (kMomentThreads - 1)) == tid) {
+    const int mine = lowest / kMomentThreads;
+#pragma unroll
+    for (int j = 0; j < kRowsPerThread; ++j)
+      if (j == mine) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k) reference[k] = px[j][k], reference[3 + k] = py[j][k];
+      }
+  }
+  __syncthreads();
+  double rx[3], ry[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    rx[k] = lowest != kNoRow ? (double)reference[k] : 0.0;
+    ry[k] = lowest != kNoRow ? (double)reference[3 + k] : 0.0;
+  }
 
   double acc[kMoments];
 #pragma unroll
   for (int m = 0; m < kMoments; ++m) acc[m] = 0.0;
 #pragma unroll
   for (int j = 0; j < kRowsPerThread; ++j) {
-    const int i = chunk * kMomentRows + j * kMomentThreads + tid;   // (chunks * kMomentRows < 2^31: N <= 2^28)
-    if (i >= nv) continue;
-    const size_t at = (size_t)b * N + i;
-    int row = i;
-    if (idx) {
-      const int k = idx[at];
-      if (k < 0 || (gather && k >= M)) continue;
-      if (gather) row = k;
-    }
-    if (sqdist && !(sqdist[at] <= max_sqdist)) continue;
-    const double w = weights ? (double)weights[at] : 1.0;
-    const double ax = (double)xb[3 * (size_t)i] - px, ay = (double)xb[3 * (size_t)i + 1] - py,
-                 az = (double)xb[3 * (size_t)i + 2] - pz;
-    const double bx = (double)yb[3 * (size_t)row] - qx, by = (double)yb[3 * (size_t)row + 1] - qy,
-                 bz = (double)yb[3 * (size_t)row + 2] - qz;
-    const double wax = w * ax, way = w * ay, waz = w * az;
-    acc[0] += w;
+    const double wj = w[j];
+    const double ax = (double)px[j][0] - rx[0], ay = (double)px[j][1] - rx[1], az = (double)px[j][2] - rx[2];
+    const double bx = (double)py[j][0] - ry[0], by = (double)py[j][1] - ry[1], bz = (double)py[j][2] - ry[2];
+    const double wax = wj * ax, way = wj * ay, waz = wj * az;
+    acc[0] += wj;
     acc[1] += wax, acc[2] += way, acc[3] += waz;
-    acc[4] += w * bx, acc[5] += w * by, acc[6] += w * bz;
+    acc[4] += wj * bx, acc[5] += wj * by, acc[6] += wj * bz;
     acc[7] += wax * bx, acc[8] += wax * by, acc[9] += wax * bz;
     acc[10] += way * bx, acc[11] += way * by, acc[12] += way * bz;
     acc[13] += waz * bx, acc[14] += waz * by, acc[15] += waz * bz;
     acc[16] += wax * ax + way * ay + waz * az;
-    acc[17] += w * (bx * bx + by * by + bz * bz);
+    acc[17] += wj * (bx * bx + by * by + bz * bz);
   }
   // the wavefront's sum in a fixed tree, then the wavefronts in ascending order
 #pragma unroll
@@ -99,7 +148,6 @@ __global__ __launch_bounds__(kMomentThreads) void k_align_moments(
     for (int step = kWave / 2; step > 0; step >>= 1) v += __shfl_down(v, step, kWave);
     acc[m] = v;
   }
-  const int lane = tid & (kWave - 1), wave = tid >> 6;
   if (lane == 0) {
 #pragma unroll
     for (int m = 0; m < kMoments; ++m) lds[wave][m] = acc[m];
@@ -109,6 +157,20 @@ __global__ __launch_bounds__(kMomentThreads) void k_align_moments(
     double v = lds[0][tid];
 #pragma unroll
     for (int wv = 1; wv < kMomentWaves; ++wv) v += lds[wv][tid];
+    sums[tid] = v;
+  }
+  __syncthreads();
+  // from the moments about the reference to the chunk's means and the moments about THEM
+  if (tid < kMoments) {
+    const double W = sums[0];
+    const bool some = W != 0.0;   // (NaN included: it has to reach the solve)
+    const double iw = some ? 1.0 / W : 0.0;
+    double v = sums[tid];
+    if (tid >= 1 && tid < 4) v = some ? rx[tid - 1] + v * iw : 0.0;
+    else if (tid >= 4 && tid < 7) v = some ? ry[tid - 4] + v * iw : 0.0;
+    else if (tid >= 7 && tid < 16) v -= sums[1 + (tid - 7) / 3] * (sums[4 + (tid - 7) % 3] * iw);
+    else if (tid == 16) v -= (sums[1] * sums[1] + sums[2] * sums[2] + sums[3] * sums[3]) * iw;
+    else if (tid == 17) v -= (sums[4] * sums[4] + sums[5] * sums[5] + sums[6] * sums[6]) * iw;
     partials[((size_t)b * gridDim.x + chunk) * kMoments + tid] = v;
   }
 }
@@ -206,37 +268,87 @@ __device__ void rotation_of(const double *c, bool allow_reflection, double *R, d
     for (int j = 0; j < 3; ++j) R[3 * i + j] = u[i][0] * v[j][0] + u[i][1] * v[j][1] + u[i][2] * v[j][2];
 }
 
-// grid (B).  The ICP bookkeeping (converged, iterations, prev_rmse) is all given or all NULL.
-__global__ __launch_bounds__(kSolveThreads) void k_align_solve(
-    const float *__restrict__ x, const float *__restrict__ y, int gather, int N, int M, int chunks,
-    const double *__restrict__ partials, int estimate_scale, int allow_reflection, double relative_rmse_thr,
-    float *__restrict__ R, float *__restrict__ T, float *__restrict__ s, float *__restrict__ rmse,
-    int32_t *__restrict__ converged, int32_t *__restrict__ iterations, double *__restrict__ prev_rmse) {
-  __shared__ double groups[kSolveGroups][kMoments];
-  __shared__ double moments[kMoments];
-  const int b = (int)blockIdx.x, tid = (int)threadIdx.x;
-  if (converged && converged[b]) return;   // (the whole workgroup) frozen
-  const int group = tid >> 5, m = tid & 31;
-  if (m < kMoments) {
-    const double *pb = partials + (size_t)b * chunks * kMoments + m;
+// The fixed-order sum of one value per chunk: eight interleaved groups of chunks, then the groups in ascending order.
+// Lane m < count of every group calls term(k, m) for its chunks; out[m] is valid after the call, for every thread.
+template <typename Term>
+__device__ __forceinline__ void sum_over_chunks(int chunks, int count, double (*groups)[kMoments], double *out,
+                                                Term term) {
+  const int tid = (int)threadIdx.x, group = tid >> 5, m = tid & 31;
+  if (m < count) {
     double v = 0.0;
-    for (int k = group; k < chunks; k += kSolveGroups) v += pb[(size_t)k * kMoments];
+    for (int k = group; k < chunks; k += kSolveGroups) v += term(k, m);
     groups[group][m] = v;
   }
   __syncthreads();
-  if (tid < kMoments) {
+  if (tid < count) {
     double v = groups[0][tid];
 #pragma unroll
     for (int g = 1; g < kSolveGroups; ++g) v += groups[g][tid];
-    moments[tid] = v;
+    out[tid] = v;
   }
   __syncthreads();
+}
+
+// grid (B).  The ICP bookkeeping (converged, iterations, prev_rmse) is all given or all NULL.
+// The chunks' (W, means, centred moments) meet in two passes, both in the fixed order: the image's means as offsets
+// from the means of its first chunk that counts anything, then every chunk's centred moments moved onto those means,
+// C_k + W_k (mx_k - xm)(my_k - ym)^T.  No row that is not counted enters anywhere, and coincident points give offsets
+// and moments of exactly 0.
+__global__ __launch_bounds__(kSolveThreads) void k_align_solve(
+    int chunks, const double *__restrict__ partials, int estimate_scale, int allow_reflection,
+    double relative_rmse_thr, float *__restrict__ R, float *__restrict__ T, float *__restrict__ s,
+    float *__restrict__ rmse, int32_t *__restrict__ converged, int32_t *__restrict__ iterations,
+    double *__restrict__ prev_rmse) {
+  __shared__ double groups[kSolveGroups][kMoments];
+  __shared__ double means[kMeanSums], centred[kCentredSums];
+  __shared__ int first_of_wave[kSolveWaves];
+  const int b = (int)blockIdx.x, tid = (int)threadIdx.x;
+  if (converged && converged[b]) return;   // (the whole workgroup) frozen
+  const double *pb = partials + (size_t)b * chunks * kMoments;
+
+  int lowest = kNoRow;   // the first chunk with W > 0
+  for (int k = tid; k < chunks; k += kSolveThreads)
+    if (pb[(size_t)k * kMoments] > 0.0) {
+      lowest = k;
+      break;
+    }
+#pragma unroll
+  for (int step = kWave / 2; step > 0; step >>= 1) lowest = min(lowest, __shfl_xor(lowest, step, kWave));
+  if ((tid & (kWave - 1)) == 0) first_of_wave[tid >> 6] = lowest;
+  __syncthreads();
+  lowest = first_of_wave[0];
+#pragma unroll
+  for (int wv = 1; wv < kSolveWaves; ++wv) lowest = min(lowest, first_of_wave[wv]);
+  double origin[6];   // of x and of y
+#pragma unroll
+  for (int k = 0; k < 6; ++k) origin[k] = lowest != kNoRow ? pb[(size_t)lowest * kMoments + 1 + k] : 0.0;
+
+  sum_over_chunks(chunks, kMeanSums, groups, means, [&](int k, int m) {
+    const double *p = pb + (size_t)k * kMoments;
+    return m == 0 ? p[0] : p[0] * (p[m] - origin[m - 1]);
+  });
+  const double W = means[0];
+  const double iw = W != 0.0 ? 1.0 / W : 0.0;
+  double offset[6];   // the image's means from the origin
+#pragma unroll
+  for (int k = 0; k < 6; ++k) offset[k] = means[1 + k] * iw;
+  sum_over_chunks(chunks, kCentredSums, groups, centred, [&](int k, int m) {
+    const double *p = pb + (size_t)k * kMoments;
+    double d[6];
+#pragma unroll
+    for (int c = 0; c < 6; ++c) d[c] = (p[1 + c] - origin[c]) - offset[c];
+    double moved;
+    if (m < 9) moved = d[m / 3] * d[3 + m % 3];
+    else if (m == 9) moved = d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
+    else moved = d[3] * d[3] + d[4] * d[4] + d[5] * d[5];
+    return p[7 + m] + p[0] * moved;
+  });
   if (tid != 0) return;
 
   float *Rb = R + (size_t)b * 9, *Tb = T + (size_t)b * 3;
   double total = 0.0;
-  for (int k = 0; k < kMoments; ++k) total += moments[k];
-  const double W = moments[0];
+  for (int k = 0; k < kMeanSums; ++k) total += means[k];
+  for (int k = 0; k < kCentredSums; ++k) total += centred[k];
   if (!(fabs(total) < (double)INFINITY)) {   // a non-finite coordinate or weight in a kept row
     for (int k = 0; k < 9; ++k) Rb[k] = NAN;
     for (int k = 0; k < 3; ++k) Tb[k] = NAN;
@@ -262,25 +374,19 @@ __global__ __launch_bounds__(kSolveThreads) void k_align_solve(
     if (rmse) rmse[b] = 0.0f;
     return;
   }
-  const float *xb = x + (size_t)b * N * 3;
-  const float *yb = y + (size_t)b * (gather ? M : N) * 3;
-  const double pivot_x[3] = {pivot_of(xb[0]), pivot_of(xb[1]), pivot_of(xb[2])};
-  const double pivot_y[3] = {pivot_of(yb[0]), pivot_of(yb[1]), pivot_of(yb[2])};
-  const double iw = 1.0 / W;
   double xm[3], ym[3], c[9];
-  for (int k = 0; k < 3; ++k) xm[k] = moments[1 + k] * iw, ym[k] = moments[4 + k] * iw;
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) c[3 * i + j] = moments[7 + 3 * i + j] * iw - xm[i] * ym[j];
-  const double var_x = fmax(moments[16] * iw - (xm[0] * xm[0] + xm[1] * xm[1] + xm[2] * xm[2]), 0.0);
-  const double var_y = fmax(moments[17] * iw - (ym[0] * ym[0] + ym[1] * ym[1] + ym[2] * ym[2]), 0.0);
+  for (int k = 0; k < 3; ++k) xm[k] = origin[k] + offset[k], ym[k] = origin[3 + k] + offset[3 + k];
+  for (int k = 0; k < 9; ++k) c[k] = centred[k] * iw;
+  const double var_x = fmax(centred[9] * iw, 0.0);
+  const double var_y = fmax(centred[10] * iw, 0.0);
   double rot[9], trace;
   rotation_of(c, allow_reflection != 0, rot, &trace);
   const double scale = (estimate_scale && var_x > 0.0) ? trace / var_x : 1.0;
   double t[3];
   for (int j = 0; j < 3; ++j) {
     double moved = 0.0;
-    for (int i = 0; i < 3; ++i) moved += (pivot_x[i] + xm[i]) * rot[3 * i + j];
-    t[j] = (pivot_y[j] + ym[j]) - scale * moved;
+    for (int i = 0; i < 3; ++i) moved += xm[i] * rot[3 * i + j];
+    t[j] = ym[j] - scale * moved;
   }
   const double mse = fmax(scale * scale * var_x - 2.0 * scale * trace + var_y, 0.0);
   const double root = sqrt(mse);
@@ -372,7 +478,7 @@ inline unsigned row_blocks(int N) {
 
 }  // namespace
 
-// the partial moments [B][chunks][18] float64
+// the chunks' partials [B][chunks][18] float64
 size_t align_ws(int B, int N) { return align_up((size_t)B * chunks_of(N) * kMoments * sizeof(double), 256); }
 
 int launch_align_solve(const float *x, const float *y, const int32_t *idx, int gather, const float *weights,
@@ -386,8 +492,8 @@ int launch_align_solve(const float *x, const float *y, const int32_t *idx, int g
                      gather, weights, sqdist, max_sqdist, lengths, converged, N, M, partials);
   int rc = check_launch();
   if (rc != MR_OK) return rc;
-  hipLaunchKernelGGL(k_align_solve, dim3((unsigned)B), dim3(kSolveThreads), 0, stream, x, y, gather, N, M, chunks,
-                     partials, estimate_scale, allow_reflection, relative_rmse_thr, R, T, s, rmse, converged, iterations,
+  hipLaunchKernelGGL(k_align_solve, dim3((unsigned)B), dim3(kSolveThreads), 0, stream, chunks, partials,
+                     estimate_scale, allow_reflection, relative_rmse_thr, R, T, s, rmse, converged, iterations,
                      prev_rmse);
   return check_launch();
 }

@@ -976,14 +976,17 @@ def _alignment_torch(x, y, weights, lengths, estimate_scale, allow_reflection):
     W = w.sum(1)
     empty = ~(W > 0) & (W == W)   # (a NaN weight is not "empty": it makes the image NaN)
     iw = 1.0 / torch.where(empty, torch.ones_like(W), W)
-    # the means about a pivot (row 0, as the kernels do): coincident points then have a variance of exactly 0
-    finite_or_zero = lambda t: torch.where(torch.isfinite(t), t, torch.zeros_like(t))
-    px, py = finite_or_zero(x[:, :1].detach()), finite_or_zero(y[:, :1].detach())
+    # the means about a reference point, the first row of positive weight (as the kernels take it per chunk): coincident
+    # points then have a variance of exactly 0, and a row that is not counted never enters.  The weight multiplies
+    # first everywhere, so that a far-away row of weight 0 contributes an exact 0 and never an overflowed product.
+    first = (w.detach() > 0).to(torch.int8).argmax(1)[:, None, None].expand(B, 1, 3)
+    px, py = torch.gather(x.detach(), 1, first), torch.gather(y.detach(), 1, first)
     xm = px[:, 0] + (w[..., None] * (x - px)).sum(1) * iw[:, None]
     ym = py[:, 0] + (w[..., None] * (y - py)).sum(1) * iw[:, None]
     xc, yc = x - xm[:, None], y - ym[:, None]
-    C = torch.einsum("bn,bni,bnj->bij", w, xc, yc) * iw[:, None, None]
-    var_x = (w * (xc * xc).sum(-1)).sum(1) * iw
+    wxc = w[..., None] * xc
+    C = torch.einsum("bni,bnj->bij", wxc, yc) * iw[:, None, None]
+    var_x = (wxc * xc).sum(-1).sum(1) * iw
     eye = torch.eye(3, dtype=x.dtype, device=x.device).expand(B, 3, 3)
     # a non-finite coordinate or weight: the image's outputs are NaN (and torch.linalg.svd never sees it)
     poisoned = ~torch.isfinite(C.detach()).all(-1).all(-1) | ~torch.isfinite(var_x.detach())
@@ -1003,6 +1006,7 @@ def _alignment_torch(x, y, weights, lengths, estimate_scale, allow_reflection):
         s = torch.ones_like(W)
     T = torch.where(empty[:, None], torch.zeros_like(ym), ym - s[:, None] * torch.einsum("bi,bij->bj", xm, R))
     residual = s[:, None, None] * (xc @ R) - yc
+    residual = torch.where((w == 0)[..., None], torch.zeros_like(residual), residual)   # (its square may overflow)
     mse = (w * (residual * residual).sum(-1)).sum(1) * iw
     nan = torch.full_like(W, float("nan"))
     R = torch.where(poisoned[:, None, None], nan[:, None, None], R)
