@@ -6,6 +6,9 @@
 //   lap  = 1/V sum_i |delta_i|,  delta_i = 1/deg_i sum_{j in N(i)} v_j - v_i      (0 for a vertex without neighbours)
 //   edge = 1/E sum_e |v_lo - v_hi|          or  1/E sum_e (|v_lo - v_hi| - target)^2
 //   nc   = 1/F sum_flaps (1 - cos(n0, n1)), n0 = (b-a) x (c-a), n1 = (d-a) x (b-a) (0 where |n0| or |n1| <= 1e-8)
+// Evaluated so that neither cancels in float32: delta_i as 1/deg_i sum_j (v_j - v_i), from differences (nothing is
+// lost against |v| far from the origin), and 1 - cos as |n0/|n0| - n1/|n1||^2 / 2 (nothing is lost against 1 across a
+// nearly flat edge).  The backward differentiates the same functions (flap_gradient: d(1 - cos) in closed form).
 //
 // Both directions are per-destination GATHERS like k_vertex_normals (mesh_ops.hip): eight lanes own one
 // (image, vertex), walk its lists eight entries a trip and meet in a fixed butterfly, so every output is written
@@ -114,10 +117,9 @@ __global__ __launch_bounds__(kThreads) void k_mesh_reg_forward(
     for (int i = e0 + sub; i < e1; i += kLanesPerVertex) {
       const int j = nbr[i];
       if ((unsigned)j >= (unsigned)V) continue;
-      const V3 vj = vb[j];
-      s = s + vj;
+      const V3 d = vb[j] - vi;
+      s = s + d;   // differences, not positions: delta_i does not cancel against |v| far from the origin
       if ((terms & kEdge) && j > v) {   // the edge (v, j) is counted here, at its lower endpoint
-        const V3 d = vi - vj;
         const float len = sqrtf(dot(d, d));
         edge += use_target ? (len - target) * (len - target) : len;
       }
@@ -129,7 +131,7 @@ __global__ __launch_bounds__(kThreads) void k_mesh_reg_forward(
         const int deg = e1 - e0;
         if (deg > 0) {
           const float inv = 1.0f / (float)deg;
-          const V3 delta = inv * s - vi;
+          const V3 delta = inv * s;
           const float len = sqrtf(dot(delta, delta));
           if (len > 0.0f) {
             lap = len;
@@ -148,7 +150,11 @@ __global__ __launch_bounds__(kThreads) void k_mesh_reg_forward(
         const V3 p = vb[q.b] - pa, qc = vb[q.c] - pa, r = vb[q.d] - pa;
         const V3 n0 = cross(p, qc), n1 = cross(r, p);
         const float l0 = sqrtf(dot(n0, n0)), l1 = sqrtf(dot(n1, n1));
-        if (l0 > kNormalFloor && l1 > kNormalFloor) nc = 1.0f - dot(n0, n1) / (l0 * l1);
+        if (l0 > kNormalFloor && l1 > kNormalFloor) {
+          // 1 - cos as |h0 - h1|^2 / 2 on the unit normals: no cancellation against 1 on a nearly flat flap
+          const V3 w = (1.0f / l0) * n0 - (1.0f / l1) * n1;
+          nc = 0.5f * dot(w, w);
+        }
       }
     }
   }

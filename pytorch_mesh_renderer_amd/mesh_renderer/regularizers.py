@@ -70,11 +70,12 @@ def _terms_torch(vertices, topology, terms, target_length):
     lo, hi = edges[:, 0], edges[:, 1]
     if terms & MESH_LAPLACIAN:
         src, dst = torch.cat([lo, hi]), torch.cat([hi, lo])
-        sums = torch.zeros_like(vertices).index_add(1, src, vertices.index_select(1, dst))
+        # the sum of v_j - v_i, as the kernel forms it: nothing cancels against |v| far from the origin
+        sums = torch.zeros_like(vertices).index_add(
+            1, src, vertices.index_select(1, dst) - vertices.index_select(1, src))
         degree = torch.zeros(V, dtype=vertices.dtype, device=vertices.device).index_add_(
             0, src, torch.ones(src.shape[0], dtype=vertices.dtype, device=vertices.device))
-        connected = (degree > 0)[None, :, None]
-        delta = torch.where(connected, sums / degree.clamp(min=1)[None, :, None] - vertices, torch.zeros_like(vertices))
+        delta = sums / degree.clamp(min=1)[None, :, None]
         lap = _safe_norm(delta).sum(1) / V
     if terms & MESH_EDGE and edges.shape[0] > 0:
         length = _safe_norm(vertices.index_select(1, lo) - vertices.index_select(1, hi))
@@ -85,8 +86,10 @@ def _terms_torch(vertices, topology, terms, target_length):
         n1 = torch.cross(d - a, b - a, dim=-1)
         l0, l1 = _safe_norm(n0), _safe_norm(n1)
         ok = (l0 > NORMAL_FLOOR) & (l1 > NORMAL_FLOOR)
-        cos = (n0 * n1).sum(-1) / torch.where(ok, l0 * l1, torch.ones_like(l0))
-        nc = torch.where(ok, 1.0 - cos, torch.zeros_like(cos)).mean(1)
+        # 1 - cos as |h0 - h1|^2 / 2 on the unit normals: no cancellation against 1 on a nearly flat flap
+        one = torch.ones_like(l0)
+        h = n0 / torch.where(ok, l0, one)[..., None] - n1 / torch.where(ok, l1, one)[..., None]
+        nc = torch.where(ok, 0.5 * (h * h).sum(-1), torch.zeros_like(l0)).mean(1)
     return torch.stack([lap, edge, nc], dim=1)
 
 
