@@ -1087,6 +1087,54 @@ int mr_winding_number_forward(const float *points, const float *vertices, const 
                               const int32_t *lengths, int B, int N, int V, int T, float *w, void *workspace,
                               size_t workspace_bytes, void *stream);
 
+/* ---- ray casting: where a ray first meets the mesh (no reference counterpart) ----
+ * Per image b, for every ray (o, d) = (origins[b,i], directions[b,i]) with i < lengths[b], over the triangles f of one
+ * shared topology with corners va, vb, vc = vertices[b, triangles[f]]: the watertight test of Woop, Benthin and Wald
+ * (2013), in float32 ("Point-cloud losses").  d is NOT normalised: t is in units of |d|, the hit point
+ * is o + t d.
+ *   per ray:     kz = the first of x, y, z that attains max |d_k|;  kx = (kz + 1) % 3, ky = (kz + 2) % 3, exchanged
+ *                when d[kz] < 0;  Sx = d[kx] / d[kz], Sy = d[ky] / d[kz], Sz = 1 / d[kz]
+ *   per corner:  p = v_P - o;  Px = fma(-Sx, p[kz], p[kx]),  Py = fma(-Sy, p[kz], p[ky]),  Pz = Sz p[kz]
+ *   edges:       U = Cx By - Cy Bx,  V = Ax Cy - Ay Cx,  W = Bx Ay - By Ax: two rounded products and one rounded
+ *                difference each, never fused, so the neighbour across a shared edge computes the exact negative.
+ *                If any of the three is exactly 0, all three are recomputed in float64 from the float32 Ax .. Cy (the
+ *                products are exact there, so the signs are), the sign test below is made on the float64 values, and
+ *                they are rounded to float32 for what follows.
+ *   acceptance:  every step is a comparison that a NaN fails.  Reject when some edge function is < 0 and some is > 0;
+ *                det = (U + V) + W, reject when det == 0;  T = (U Az + V Bz) + W Cz (each operation rounded),
+ *                t = T / det rounded once; accept when t >= t_min && t <= t_max; -0 is stored as +0.
+ *                bary = (U, V, W) / det.
+ * The first hit is the accepted triangle with the least t; equal t goes to the lowest face; a t of +inf is no hit.
+ * A triangle with an index outside [0, V), two equal indices or a corner that is not finite is never hit.  A ray
+ * without a hit -- a padded row, a non-finite origin or direction, a zero direction, nothing in [t_min, t_max] --
+ * gets t = +inf, face = -1, bary = 0.  No back-face culling.  0 <= t_min <= t_max, else MR_EINVAL.
+ * A ray's t, face and bary are the same bit for bit whatever the launch shape or the batch the image sat in: a finish
+ * pass evaluates the chosen pair once more with the search's own functions.
+ *   origins, directions [B,N,3], vertices [B,V,3] f32;  triangles [T,3] i32;  lengths [B] i32 (device) or NULL = all N
+ *   t [B,N] f32, face [B,N] i32, bary [B,N,3] f32 out
+ * mr_cast_rays_plan: the launch shape, a pure host function, as mr_winding_number_plan; with splits > 1 the runs of
+ * triangles meet through one 64-bit (t bits, face) key per (image, split, ray), written with plain stores and merged
+ * by a second launch: no atomics, stream order only, capturable.  The workspace holds the per-image corner records (48
+ * bytes each) and those keys; 16-byte aligned, needed by every forward call.
+ * Backward, the face held fixed: with n = (vb - va) x (vc - va) and g = n / (n . d)
+ *   dorigins[b,i] = -grad_t[b,i] g,  ddirections[b,i] = -grad_t[b,i] t[b,i] g,
+ *   dvertices[b,v] = sum over the (ray, corner k) that name v of grad_t[b,i] bary[b,i,k] g
+ * 0, never NaN, for a ray without a hit, with n . d == 0 or with a g that is not finite.  Any of the three outputs may
+ * be NULL (not computed).  dvertices is a gather over order [B,3N] / offsets [B,V+1], the inverted index of the
+ * (ray, corner) entries keyed by vertex as mr_nearest_triangle_backward takes it; bitwise reproducible.
+ * Size limits: those of mr_winding_number_*; sizes outside are MR_EINVAL (queries return 0). */
+int mr_cast_rays_plan(int B, int N, int T, int *splits, int *queries_per_lane, int *triangle_tile,
+                      int *workgroup_size);
+size_t mr_cast_rays_workspace_bytes(int B, int N, int T);
+int mr_cast_rays_forward(const float *origins, const float *directions, const float *vertices,
+                         const int32_t *triangles, const int32_t *lengths, int B, int N, int V, int T, float t_min,
+                         float t_max, float *t, int32_t *face, float *bary, void *workspace, size_t workspace_bytes,
+                         void *stream);
+int mr_cast_rays_backward(const float *directions, const float *vertices, const int32_t *triangles,
+                          const int32_t *lengths, int B, int N, int V, int T, const float *t, const int32_t *face,
+                          const float *bary, const int32_t *order, const int32_t *offsets, const float *grad_t,
+                          float *dorigins, float *ddirections, float *dvertices, void *stream);
+
 /* ---- clip-space transforms --------------------------------------------------------------
  * perspective(aspect, fov_y, near, far) . look_at(eye, center, up) per image, the product render() and
  * rasterize() apply to the vertices (src/common/camera_utils.py:45-139; src/mesh_renderer/render.py

@@ -455,6 +455,18 @@ def lib():
         except AttributeError as e:   # the winding-number entry points came without an ABI version bump
             raise NativeLibraryError("%s lacks the winding-number entry points (%s): rebuild it (make -C "
                                      "pytorch_mesh_renderer_amd/csrc)" % (LIB_PATH, e))
+        try:
+            L.mr_cast_rays_plan.argtypes = [ci] * 3 + [vp] * 4
+            L.mr_cast_rays_plan.restype = ci
+            L.mr_cast_rays_workspace_bytes.argtypes = [ci] * 3
+            L.mr_cast_rays_workspace_bytes.restype = sz
+            L.mr_cast_rays_forward.argtypes = [vp] * 5 + [ci] * 4 + [cf, cf] + [vp] * 4 + [sz, vp]
+            L.mr_cast_rays_forward.restype = ci
+            L.mr_cast_rays_backward.argtypes = [vp] * 4 + [ci] * 4 + [vp] * 10
+            L.mr_cast_rays_backward.restype = ci
+        except AttributeError as e:   # the ray-casting entry points came without an ABI version bump
+            raise NativeLibraryError("%s lacks the ray-casting entry points (%s): rebuild it (make -C "
+                                     "pytorch_mesh_renderer_amd/csrc)" % (LIB_PATH, e))
         _lib = L
     return _lib
 
@@ -1701,6 +1713,77 @@ def winding_number_forward(points, vertices, triangles, lengths=None):
                                          _ptr(w), _ptr(ws), have, _stream(dev))
     _check(rc, "mr_winding_number_forward")
     return w
+
+
+def cast_rays_plan(B, N, T):
+    """The launch shape mr_cast_rays_forward takes for B images of N rays against T triangles, a pure host function:
+    {"splits", "queries_per_lane", "triangle_tile", "workgroup_size"} (include/mesh_raster.h).  The size limits are
+    the winding number's."""
+    return _plan("cast_rays_plan", (B, N, T), ("splits", "queries_per_lane", "triangle_tile", "workgroup_size"),
+                 "1..65535 images of 1..2^28 rays and 1..2^24 triangles")
+
+
+def _chk_rays(origins, directions, vertices, triangles, lengths):
+    B, N, V, T = _chk_point_mesh(origins, vertices, triangles, lengths)
+    _chk("directions", directions, _F32, B, N, 3)
+    if T > 1 << 24:
+        raise ValueError("ray casting takes at most 2^24 triangles, got %d" % T)
+    return B, N, V, T
+
+
+def cast_rays_forward(origins, directions, vertices, triangles, lengths=None, t_min=0.0, t_max=float("inf")):
+    """origins, directions [B,N,3], vertices [B,V,3] f32, triangles [T,3] i32, lengths [B] i32 or None (device) ->
+    (t [B,N] f32, face [B,N] i32, bary [B,N,3] f32), +inf / -1 / 0 for a ray without a hit: mr_cast_rays_forward."""
+    B, N, V, T = _chk_rays(origins, directions, vertices, triangles, lengths)
+    if not 0.0 <= t_min <= t_max:
+        raise ValueError("0 <= t_min <= t_max is required, got %r and %r" % (t_min, t_max))
+    dev = _require_device(origins, directions, vertices, triangles, *([lengths] if lengths is not None else []))
+    L = lib()
+    origins, directions = origins.contiguous(), directions.contiguous()
+    vertices, triangles = vertices.contiguous(), triangles.contiguous()
+    lengths = lengths.contiguous() if lengths is not None else None
+    t = torch.empty(B, N, dtype=_F32, device=dev)
+    face = torch.empty(B, N, dtype=_I32, device=dev)
+    bary = torch.empty(B, N, 3, dtype=_F32, device=dev)
+    with torch.cuda.device(dev):
+        ws, have = _workspace(dev, L.mr_cast_rays_workspace_bytes(B, N, T))
+        rc = L.mr_cast_rays_forward(_ptr(origins), _ptr(directions), _ptr(vertices), _ptr(triangles), _ptr(lengths), B,
+                                    N, V, T, float(t_min), float(t_max), _ptr(t), _ptr(face), _ptr(bary), _ptr(ws),
+                                    have, _stream(dev))
+    _check(rc, "mr_cast_rays_forward")
+    return t, face, bary
+
+
+def cast_rays_backward(directions, vertices, triangles, lengths, t, face, bary, grad_t, index=None, want_dorigins=True,
+                       want_ddirections=True, want_dvertices=True):
+    """mr_cast_rays_backward -> (dorigins [B,N,3], ddirections [B,N,3], dvertices [B,V,3]), None for what is not
+    wanted.  index: (order [B,3N], offsets [B,V+1]), nearest_inverted_index() of the (ray, corner) entries' vertices,
+    needed for dvertices."""
+    B, N, V, T = _chk_rays(directions, directions, vertices, triangles, lengths)   # the backward takes no origins
+    _chk("t", t, _F32, B, N)
+    _chk("face", face, _I32, B, N)
+    _chk("bary", bary, _F32, B, N, 3)
+    _chk("upstream gradient", grad_t, _F32, B, N)
+    tensors = [directions, vertices, triangles, t, face, bary, grad_t] + ([lengths] if lengths is not None else [])
+    if index is not None:
+        _chk("order", index[0], _I32, B, 3 * N)
+        _chk("offsets", index[1], _I32, B, V + 1)
+        tensors += list(index)
+    elif want_dvertices:
+        raise ValueError("dvertices needs the inverted index of the named corners")
+    dev = _require_device(*tensors)
+    L = lib()
+    c = lambda x: x.contiguous() if x is not None else None
+    order, offsets = index if index is not None else (None, None)
+    dorigins = torch.empty(B, N, 3, dtype=_F32, device=dev) if want_dorigins else None
+    ddirections = torch.empty(B, N, 3, dtype=_F32, device=dev) if want_ddirections else None
+    dvertices = torch.empty(B, V, 3, dtype=_F32, device=dev) if want_dvertices else None
+    held = [c(x) for x in (directions, vertices, triangles, lengths, t, face, bary, order, offsets, grad_t)]
+    with torch.cuda.device(dev):
+        rc = L.mr_cast_rays_backward(*[_ptr(x) for x in held[:4]], B, N, V, T, *[_ptr(x) for x in held[4:]],
+                                     _ptr(dorigins), _ptr(ddirections), _ptr(dvertices), _stream(dev))
+    _check(rc, "mr_cast_rays_backward")
+    return dorigins, ddirections, dvertices
 
 
 def nearest_point_of_triangle_plan(B, N, T):

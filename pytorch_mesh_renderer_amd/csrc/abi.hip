@@ -1159,6 +1159,46 @@ int mr_winding_number_forward(const float *points, const float *vertices, const 
                                            (hipStream_t)stream);
 }
 
+// ray casting keeps the winding number's size limits
+int mr_cast_rays_plan(int B, int N, int T, int *splits, int *queries_per_lane, int *triangle_tile,
+                      int *workgroup_size) {
+  if (bad_winding_number_dims(B, N, T) || !splits || !queries_per_lane || !triangle_tile || !workgroup_size)
+    return MR_EINVAL;
+  mr::cast_rays_plan(B, N, T, splits, queries_per_lane, triangle_tile, workgroup_size);
+  return MR_OK;
+}
+
+size_t mr_cast_rays_workspace_bytes(int B, int N, int T) {
+  if (bad_winding_number_dims(B, N, T)) return 0;
+  return mr::cast_rays_ws(B, N, T);
+}
+
+int mr_cast_rays_forward(const float *origins, const float *directions, const float *vertices,
+                         const int32_t *triangles, const int32_t *lengths, int B, int N, int V, int T, float t_min,
+                         float t_max, float *t, int32_t *face, float *bary, void *workspace, size_t workspace_bytes,
+                         void *stream) {
+  if (bad_nearest_triangle_dims(B, N, V, T) || bad_winding_number_dims(B, N, T)) return MR_EINVAL;
+  if (!origins || !directions || !vertices || !triangles || !t || !face || !bary) return MR_EINVAL;
+  if (!(t_min >= 0.0f && t_min <= t_max)) return MR_EINVAL;   // a NaN fails
+  const int rc = check_ws(workspace, workspace_bytes, mr::cast_rays_ws(B, N, T));
+  if (rc != MR_OK) return rc;
+  if (misaligned(workspace, 16)) return MR_EINVAL;   // the records are read as 16-byte words
+  return mr::launch_cast_rays_forward(origins, directions, vertices, triangles, lengths, B, N, V, T, t_min, t_max, t,
+                                      face, bary, workspace, (hipStream_t)stream);
+}
+
+int mr_cast_rays_backward(const float *directions, const float *vertices, const int32_t *triangles,
+                          const int32_t *lengths, int B, int N, int V, int T, const float *t, const int32_t *face,
+                          const float *bary, const int32_t *order, const int32_t *offsets, const float *grad_t,
+                          float *dorigins, float *ddirections, float *dvertices, void *stream) {
+  if (bad_nearest_triangle_dims(B, N, V, T) || bad_winding_number_dims(B, N, T)) return MR_EINVAL;
+  if (!directions || !vertices || !triangles || !t || !face || !bary || !grad_t) return MR_EINVAL;
+  if ((order == nullptr) != (offsets == nullptr)) return MR_EINVAL;
+  if (dvertices && !order) return MR_EINVAL;                      // the vertices' gradient is a gather over the index
+  return mr::launch_cast_rays_backward(directions, vertices, triangles, lengths, B, N, V, T, t, face, bary, order,
+                                       offsets, grad_t, dorigins, ddirections, dvertices, (hipStream_t)stream);
+}
+
 int mr_nearest_point_of_triangle_plan(int B, int N, int T, int *splits, int *points_per_step, int *point_tile,
                                       int *workgroup_size) {
   if (bad_nearest_dims(B, N, T) || !splits || !points_per_step || !point_tile || !workgroup_size) return MR_EINVAL;

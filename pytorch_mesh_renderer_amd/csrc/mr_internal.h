@@ -332,6 +332,17 @@ int launch_winding_number_forward(const float *points, const float *vertices, co
                                   const int32_t *lengths, int B, int N, int V, int T, float *w, void *ws,
                                   hipStream_t s);
 
+// ray casting, mr_cast_rays_* (nearest.hip): the winding number's launch shape, records and size limits
+void cast_rays_plan(int B, int N, int T, int *splits, int *queries_per_lane, int *triangle_tile, int *workgroup);
+size_t cast_rays_ws(int B, int N, int T);
+int launch_cast_rays_forward(const float *origins, const float *directions, const float *vertices,
+                             const int32_t *triangles, const int32_t *lengths, int B, int N, int V, int T, float t_min,
+                             float t_max, float *t, int32_t *face, float *bary, void *ws, hipStream_t s);
+int launch_cast_rays_backward(const float *directions, const float *vertices, const int32_t *triangles,
+                              const int32_t *lengths, int B, int N, int V, int T, const float *t, const int32_t *face,
+                              const float *bary, const int32_t *order, const int32_t *offsets, const float *grad_t,
+                              float *dorigins, float *ddirections, float *dvertices, hipStream_t s);
+
 // triangle to nearest point, mr_nearest_point_of_triangle_* (nearest.hip)
 void nearest_point_of_triangle_plan(int B, int N, int T, int *splits, int *points_per_step, int *point_tile,
                                     int *workgroup);

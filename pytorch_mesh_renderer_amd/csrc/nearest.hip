@@ -4,7 +4,8 @@
 // from the triangles to the points (mr_nearest_point_of_triangle_forward / _backward: "triangle to point"), and the
 // K-neighbour form of the point search (mr_knn_forward / _backward: "K nearest neighbours"), and the winding number
 // of the mesh around every point (mr_winding_number_forward: "winding number"): the same all-pairs loop with '+' where
-// the searches have 'min'.
+// the searches have 'min', and the first triangle a ray meets (mr_cast_rays_forward / _backward: "ray casting"): the
+// search once more, with the watertight ray-triangle test for the distance.
 //
 // Per image b, for every query x_i (i < x_lengths[b]) over the targets y_j (j < y_lengths[b]):
 //   sqdist_i = min_j (x_i - y_j).(x_i - y_j),   idx_i = the lowest j that attains it
@@ -1109,7 +1110,9 @@ __device__ __forceinline__ void wn_terms(F px, F py, F pz, float4 r0, float4 r1,
   den = fma_of(ca, lb, fma_of(bc, la, fma_of(ab, lc, la * lb * lc)));
 }
 
-// grid (ceil(T / kThreads), B): records [B, T, kWnRecWords] of 16-byte words
+// grid (ceil(T / kThreads), B): records [B, T, kWnRecWords] of 16-byte words.  kFiniteOnly (the ray caster's rule): a
+// triangle with a corner that is not finite is skipped too.
+template <bool kFiniteOnly>
 __global__ __launch_bounds__(kThreads) void k_wn_setup(const V3 *__restrict__ vertices,
                                                        const int32_t *__restrict__ triangles, int V, int T,
                                                        float4 *__restrict__ records) {
@@ -1117,12 +1120,22 @@ __global__ __launch_bounds__(kThreads) void k_wn_setup(const V3 *__restrict__ ve
   if (t >= T) return;
   float4 *out = records + ((size_t)b * T + t) * kWnRecWords;
   int ia, ib, ic;
-  if (!usable_triangle(triangles, t, V, ia, ib, ic) || ia == ib || ib == ic || ic == ia) {
+  bool usable = usable_triangle(triangles, t, V, ia, ib, ic) && ia != ib && ib != ic && ic != ia;
+  V3 a = {0.0f, 0.0f, 0.0f}, p = a, c = a;
+  if (usable) {
+    const V3 *vb = vertices + (size_t)b * V;
+    a = vb[ia], p = vb[ib], c = vb[ic];
+    if constexpr (kFiniteOnly) {
+      // x * 0 is NaN for an infinite or NaN x
+      const float sum = ((a.x * 0.0f + a.y * 0.0f) + (a.z * 0.0f + p.x * 0.0f)) + ((p.y * 0.0f + p.z * 0.0f) +
+                        (c.x * 0.0f + c.y * 0.0f)) + c.z * 0.0f;
+      usable = sum == 0.0f;
+    }
+  }
+  if (!usable) {
     out[0] = out[1] = out[2] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);   // skipped: contributes nothing
     return;
   }
-  const V3 *vb = vertices + (size_t)b * V;
-  const V3 a = vb[ia], p = vb[ib], c = vb[ic];
   out[0] = make_float4(a.x, a.y, a.z, 1.0f);
   out[1] = make_float4(p.x, p.y, p.z, 0.0f);
   out[2] = make_float4(c.x, c.y, c.z, 0.0f);
@@ -1209,6 +1222,324 @@ __global__ __launch_bounds__(kThreads) void k_wn_merge(const long long *__restri
   }
   const bool valid = i < valid_count(lengths, b, N);
   w[(size_t)b * N + i] = !valid ? 0.0f : (poisoned ? __int_as_float(0x7fc00000) : wn_to_float(sum));
+}
+
+// ---- ray casting ------------------------------------------------------------------------------------------------
+// mr_cast_rays_forward / _backward: per image, for every ray (o, d) the first triangle of the mesh it meets, the
+// parameter t of the hit point o + t d (d is NOT normalised) and its barycentrics, by the watertight test of Woop,
+// Benthin and Wald (2013); the definition stands in include/mesh_raster.h and INTEGRATION.md, "Point-cloud losses".
+// It is k_nt_search's all-pairs loop over k_wn_setup's 48-byte corner records (with kFiniteOnly: a non-finite corner
+// skips the triangle too): 128 records staged in LDS, every lane reads the same record (a broadcast) and keeps one
+// ray, or two in packed fp32.  A ray's axis choice (kx, ky, kz) is per-lane data and reaches the corners through
+// selects (pick_of): the 2 x 3 shear matrix would need its fma chain to END on the inexact product -S p[kz], and which
+// column that is differs from lane to lane, so a fixed chain rounds twice where the definition rounds once.  The
+// common path of a pair is nine subtractions, the selects, six fused multiply-adds, six products, three differences
+// and one sign test (ray_edges, compiled without contraction: the neighbour across a shared edge computes the exact
+// negative); det, T, the division, the interval and the float64 recomputation of exact zeros (ray_accept, scalar code
+// per ray) sit behind a branch that a skipped record and a dead ray never take.  Faces ascending with a strict '<':
+// the lowest face of equal t.  t >= t_min >= 0 and -0 is stored as +0, so the bits of t order like the values and
+// the splits meet through key_of / k_nearest_merge.  k_ray_finish evaluates the chosen pair once more with the SAME
+// two functions -- their arithmetic is IEEE-exact operation by operation, so the scalar and the packed instantiation
+// agree bit for bit -- and writes t, face and bary: a ray's t is the same whatever the split or the batch.
+//
+// Backward, the face held fixed: with n = (b - a) x (c - a) and g = n / (n . d),  dt/do = -g,  dt/dd = -t g,
+// dt/dv_k = bary_k g; 0 where n . d is 0 or g is not finite.  One row per ray for the first two, a gather over the
+// inverted index of the 3N (ray, corner) entries keyed by vertex for the third (gather_rows), as k_nt_backward_*.
+struct Ray {
+  float ox, oy, oz;   // the origin
+  float sx, sy, sz;   // d[kx] / d[kz], d[ky] / d[kz], 1 / d[kz]
+  int kx, ky, kz;
+  bool live;          // false: a padded row, a non-finite origin or direction, a zero direction -- never hits
+};
+
+__device__ __forceinline__ bool finite3(V3 v) { return (v.x * 0.0f + v.y * 0.0f) + v.z * 0.0f == 0.0f; }
+__device__ __forceinline__ float pick(int k, float x, float y, float z) { return k == 0 ? x : (k == 1 ? y : z); }
+
+__device__ __forceinline__ Ray ray_of(V3 o, V3 d, bool have) {
+  Ray r;
+  const float ax = fabsf(d.x), ay = fabsf(d.y), az = fabsf(d.z);
+  const float m = fmaxf(ax, fmaxf(ay, az));
+  r.live = have && finite3(o) && finite3(d) && m > 0.0f;
+  r.kz = ax == m ? 0 : (ay == m ? 1 : 2);   // the first axis that attains max |d_k|
+  int kx = r.kz == 2 ? 0 : r.kz + 1, ky = kx == 2 ? 0 : kx + 1;
+  const float dz = pick(r.kz, d.x, d.y, d.z);
+  if (dz < 0.0f) {
+    const int k = kx;
+    kx = ky, ky = k;
+  }
+  r.kx = kx, r.ky = ky;
+  r.sx = r.live ? pick(kx, d.x, d.y, d.z) / dz : 0.0f;
+  r.sy = r.live ? pick(ky, d.x, d.y, d.z) / dz : 0.0f;
+  r.sz = r.live ? 1.0f / dz : 0.0f;
+  r.ox = r.live ? o.x : 0.0f, r.oy = r.live ? o.y : 0.0f, r.oz = r.live ? o.z : 0.0f;
+  return r;
+}
+
+// One (float) or two (F2) rays of a lane as ray_edges takes them: -Sx, -Sy and the origin per half, the axes per ray.
+template <typename F>
+struct RayLanes {
+  F ox, oy, oz, nsx, nsy;
+  int kx[sizeof(F) / sizeof(float)], ky[sizeof(F) / sizeof(float)], kz[sizeof(F) / sizeof(float)];
+};
+
+__device__ __forceinline__ void set_part(float &v, int, float x) { v = x; }
+__device__ __forceinline__ void set_part(F2 &v, int q, float x) {
+  if (q == 0)
+    v.x = x;
+  else
+    v.y = x;
+}
+
+template <typename F>
+__device__ __forceinline__ void set_ray(RayLanes<F> &lanes, int q, const Ray &r) {
+  set_part(lanes.ox, q, r.ox), set_part(lanes.oy, q, r.oy), set_part(lanes.oz, q, r.oz);
+  set_part(lanes.nsx, q, -r.sx), set_part(lanes.nsy, q, -r.sy);
+  lanes.kx[q] = r.kx, lanes.ky[q] = r.ky, lanes.kz[q] = r.kz;
+}
+
+__device__ __forceinline__ float pick_of(const int *k, float x, float y, float z) { return pick(k[0], x, y, z); }
+__device__ __forceinline__ F2 pick_of(const int *k, F2 x, F2 y, F2 z) {
+  return F2{pick(k[0], x.x, y.x, z.x), pick(k[1], x.y, y.y, z.y)};
+}
+
+// The sheared corners and the edge functions of one triangle (its record's three words) for one or two rays.
+template <typename F>
+struct RayEdges {
+  F ax, ay, bx, by, cx, cy;   // Px = fma(-Sx, p[kz], p[kx]), Py = fma(-Sy, p[kz], p[ky]) with p = corner - o
+  F ak, bk, ck;               // p[kz]: Pz = Sz p[kz] is formed by ray_accept
+  F u, v, w;
+};
+
+template <typename F>
+__device__ __forceinline__ RayEdges<F> ray_edges(const RayLanes<F> &ray, float4 r0, float4 r1, float4 r2) {
+#pragma clang fp contract(off)   // U, V, W: two rounded products and one rounded difference each, never fused
+  RayEdges<F> e;
+  const F pax = (F)r0.x - ray.ox, pay = (F)r0.y - ray.oy, paz = (F)r0.z - ray.oz;
+  const F pbx = (F)r1.x - ray.ox, pby = (F)r1.y - ray.oy, pbz = (F)r1.z - ray.oz;
+  const F pcx = (F)r2.x - ray.ox, pcy = (F)r2.y - ray.oy, pcz = (F)r2.z - ray.oz;
+  e.ak = pick_of(ray.kz, pax, pay, paz);
+  e.bk = pick_of(ray.kz, pbx, pby, pbz);
+  e.ck = pick_of(ray.kz, pcx, pcy, pcz);
+  e.ax = fma_of(ray.nsx, e.ak, pick_of(ray.kx, pax, pay, paz));
+  e.ay = fma_of(ray.nsy, e.ak, pick_of(ray.ky, pax, pay, paz));
+  e.bx = fma_of(ray.nsx, e.bk, pick_of(ray.kx, pbx, pby, pbz));
+  e.by = fma_of(ray.nsy, e.bk, pick_of(ray.ky, pbx, pby, pbz));
+  e.cx = fma_of(ray.nsx, e.ck, pick_of(ray.kx, pcx, pcy, pcz));
+  e.cy = fma_of(ray.nsy, e.ck, pick_of(ray.ky, pcx, pcy, pcz));
+  e.u = e.cx * e.by - e.cy * e.bx;
+  e.v = e.ax * e.cy - e.ay * e.cx;
+  e.w = e.bx * e.ay - e.by * e.ax;
+  return e;
+}
+
+// True when some edge function is below 0 and some above: the pair is rejected.  A NaN is neither.
+template <typename T>
+__device__ __forceinline__ bool mixed_signs(T u, T v, T w) {
+  return (u < 0 || v < 0 || w < 0) && (u > 0 || v > 0 || w > 0);
+}
+
+struct RayHit {
+  float t, u, v, w;   // u, v, w: the barycentrics
+};
+
+// Everything after the edge functions for part q of e, in scalar code: the float64 recomputation when an edge function
+// is exactly 0, the sign test, det, T, the division and the interval.  True: the pair is accepted.
+template <typename F>
+__device__ __forceinline__ bool ray_accept(const RayEdges<F> &e, int q, float sz, float tmin, float tmax, RayHit &h) {
+#pragma clang fp contract(off)
+  float U = part_of(e.u, q), V = part_of(e.v, q), W = part_of(e.w, q);
+  if (U == 0.0f || V == 0.0f || W == 0.0f) {
+    // the products of two floats are exact in float64, so the signs of the differences are
+    const double ax = part_of(e.ax, q), ay = part_of(e.ay, q), bx = part_of(e.bx, q), by = part_of(e.by, q);
+    const double cx = part_of(e.cx, q), cy = part_of(e.cy, q);
+    const double u = cx * by - cy * bx, v = ax * cy - ay * cx, w = bx * ay - by * ax;
+    if (mixed_signs(u, v, w)) return false;
+    U = (float)u, V = (float)v, W = (float)w;
+  } else if (mixed_signs(U, V, W)) {
+    return false;
+  }
+  const float det = (U + V) + W;
+  if (det == 0.0f) return false;
+  const float az = sz * part_of(e.ak, q), bz = sz * part_of(e.bk, q), cz = sz * part_of(e.ck, q);
+  const float T = (U * az + V * bz) + W * cz;
+  const float t = T / det;
+  if (!(t >= tmin && t <= tmax)) return false;   // a NaN fails
+  h.t = t == 0.0f ? 0.0f : t;                    // -0 is stored as +0
+  h.u = U / det, h.v = V / det, h.w = W / det;
+  return true;
+}
+
+// grid (query blocks, splits, B).  keys != null (splits > 1): one key per (image, split, ray) for k_nearest_merge;
+// keys == null: the face, -1 for a ray without a hit in this launch's triangles.
+template <typename F>
+__global__ __launch_bounds__(kThreads) void k_ray_search(const float *__restrict__ origins,
+                                                         const float *__restrict__ directions,
+                                                         const float4 *__restrict__ records,
+                                                         const int32_t *__restrict__ lengths, int N, int T, int chunk,
+                                                         float tmin, float tmax, int32_t *__restrict__ face,
+                                                         unsigned long long *__restrict__ keys) {
+  constexpr int Q = (int)(sizeof(F) / sizeof(float));
+  __shared__ float4 tile[kTriTile * kWnRecWords];
+  const int b = (int)blockIdx.z, split = (int)blockIdx.y;
+  const int nv = valid_count(lengths, b, N);
+  const float4 *rb = records + (size_t)b * T * kWnRecWords;
+  const Range run = split_range(split, chunk, T);
+  const int i0 = (int)blockIdx.x * (kThreads * Q) + (int)threadIdx.x;
+
+  float ox[Q], oy[Q], oz[Q], dx[Q], dy[Q], dz[Q], sz[Q], best[Q];
+  int bi[Q];
+  bool live[Q];
+  load_queries<Q>(origins + (size_t)b * N * 3, i0, nv, ox, oy, oz);
+  load_queries<Q>(directions + (size_t)b * N * 3, i0, nv, dx, dy, dz);
+  RayLanes<F> ray;
+#pragma unroll
+  for (int q = 0; q < Q; ++q) {
+    const Ray r = ray_of(V3{ox[q], oy[q], oz[q]}, V3{dx[q], dy[q], dz[q]}, i0 + q * kThreads < nv);
+    set_ray(ray, q, r);
+    sz[q] = r.sz;
+    live[q] = r.live;
+    best[q] = INFINITY;
+    bi[q] = -1;
+  }
+
+  for (int t0 = run.j0; t0 < run.j1; t0 += kTriTile) {
+    const int count = min(kTriTile, run.j1 - t0);
+    __syncthreads();
+    for (int f = (int)threadIdx.x; f < count * kWnRecWords; f += kThreads)
+      tile[f] = rb[(size_t)t0 * kWnRecWords + f];
+    __syncthreads();
+    for (int j = 0; j < count; ++j) {
+      const float4 *r = &tile[j * kWnRecWords];   // one address for the wavefront
+      const float4 r0 = r[0];
+      const RayEdges<F> e = ray_edges<F>(ray, r0, r[1], r[2]);
+#pragma unroll
+      for (int q = 0; q < Q; ++q) {
+        const float u = part_of(e.u, q), v = part_of(e.v, q), w = part_of(e.w, q);
+        const float lo = fminf(u, fminf(v, w)), hi = fmaxf(u, fmaxf(v, w));
+        // rare: the pair passes the sign test (or holds a NaN); a skipped record (all its edge functions are 0)
+        // and a dead ray stay out
+        if (__builtin_expect(r0.w != 0.0f && live[q] && !(lo < 0.0f && hi > 0.0f), 0)) {
+          RayHit h;
+          if (ray_accept(e, q, sz[q], tmin, tmax, h) && h.t < best[q]) {   // strict, faces ascending: the lowest face
+            best[q] = h.t;
+            bi[q] = t0 + j;
+          }
+        }
+      }
+    }
+  }
+
+#pragma unroll
+  for (int q = 0; q < Q; ++q) {
+    const int i = i0 + q * kThreads;
+    if (i >= N) continue;
+    const bool found = i < nv && bi[q] >= 0;
+    if (keys)
+      keys[((size_t)b * gridDim.y + split) * N + i] = found ? key_of(best[q], bi[q]) : kNoKey;
+    else
+      face[(size_t)b * N + i] = found ? bi[q] : -1;
+  }
+}
+
+// The chosen pair of every ray once more, with the search's own functions -> t, face, bary; +inf / -1 / 0 for a ray
+// without a hit.  grid (ceil(N / kThreads), B)
+__global__ __launch_bounds__(kThreads) void k_ray_finish(const V3 *__restrict__ origins,
+                                                         const V3 *__restrict__ directions,
+                                                         const float4 *__restrict__ records,
+                                                         const int32_t *__restrict__ lengths, int N, int T, float tmin,
+                                                         float tmax, float *__restrict__ t, int32_t *__restrict__ face,
+                                                         V3 *__restrict__ bary) {
+  const int b = (int)blockIdx.y;
+  const int i = (int)blockIdx.x * kThreads + (int)threadIdx.x;
+  if (i >= N) return;
+  const size_t row = (size_t)b * N + i;
+  const int f = i < valid_count(lengths, b, N) ? face[row] : -1;
+  RayHit h;
+  bool hit = false;
+  if ((unsigned)f < (unsigned)T) {
+    const Ray r = ray_of(origins[row], directions[row], true);
+    const float4 *rec = records + ((size_t)b * T + f) * kWnRecWords;
+    const float4 r0 = rec[0];
+    if (r.live && r0.w != 0.0f) {
+      RayLanes<float> ray;
+      set_ray(ray, 0, r);
+      hit = ray_accept(ray_edges<float>(ray, r0, rec[1], rec[2]), 0, r.sz, tmin, tmax, h);
+    }
+  }
+  t[row] = hit ? h.t : INFINITY;
+  face[row] = hit ? f : -1;
+  bary[row] = hit ? V3{h.u, h.v, h.w} : V3{0.0f, 0.0f, 0.0f};
+}
+
+// g = n / (n . d) of ray i's face, n = (b - a) x (c - a).  False -- a zero gradient -- for a row without a face, a
+// face that is not usable, n . d == 0 and a g that is not finite.  nv: the image's valid rays.
+__device__ __forceinline__ bool ray_gradient(const V3 *__restrict__ vb, const int32_t *__restrict__ triangles,
+                                             const int32_t *__restrict__ fb, const V3 *__restrict__ db, int i, int nv,
+                                             int V, int T, V3 &g) {
+  if (i >= nv) return false;
+  const int f = fb[i];
+  if ((unsigned)f >= (unsigned)T) return false;
+  int ia, ib, ic;
+  if (!usable_triangle(triangles, f, V, ia, ib, ic)) return false;
+  const V3 a = vb[ia], p = vb[ib], c = vb[ic], d = db[i];
+  const float e0x = p.x - a.x, e0y = p.y - a.y, e0z = p.z - a.z;
+  const float e1x = c.x - a.x, e1y = c.y - a.y, e1z = c.z - a.z;
+  const float nx = e0y * e1z - e0z * e1y, ny = e0z * e1x - e0x * e1z, nz = e0x * e1y - e0y * e1x;
+  const float s = nx * d.x + ny * d.y + nz * d.z;
+  if (s == 0.0f) return false;
+  g = V3{nx / s, ny / s, nz / s};
+  return finite3(g);
+}
+
+// dorigins[b, i] = -g_i G_i and ddirections[b, i] = -g_i t_i G_i (either may be null), g_i the upstream gradient of
+// t_i and G_i ray_gradient's vector; 0 for a ray without a hit.  grid (ceil(N / kThreads), B)
+__global__ __launch_bounds__(kThreads) void k_ray_backward_rays(
+    const V3 *__restrict__ directions, const V3 *__restrict__ vertices, const int32_t *__restrict__ triangles,
+    const int32_t *__restrict__ lengths, int N, int V, int T, const float *__restrict__ t,
+    const int32_t *__restrict__ face, const float *__restrict__ g_t, V3 *__restrict__ dorigins,
+    V3 *__restrict__ ddirections) {
+  const int b = (int)blockIdx.y;
+  const int i = (int)blockIdx.x * kThreads + (int)threadIdx.x;
+  if (i >= N) return;
+  const size_t row = (size_t)b * N + i;
+  V3 dorigin = {0.0f, 0.0f, 0.0f}, ddirection = dorigin, g;
+  if (ray_gradient(vertices + (size_t)b * V, triangles, face + (size_t)b * N, directions + (size_t)b * N, i,
+                   valid_count(lengths, b, N), V, T, g)) {
+    const float up = -g_t[row], upt = up * t[row];
+    dorigin = V3{up * g.x, up * g.y, up * g.z};
+    ddirection = V3{upt * g.x, upt * g.y, upt * g.z};
+  }
+  if (dorigins) dorigins[row] = dorigin;
+  if (ddirections) ddirections[row] = ddirection;
+}
+
+// dvertices[b, v] = sum over the (ray, corner) entries that name v of g_i bary_ik G_i: order [B, 3N] holds the entries
+// 3 i + k grouped by vertex, each group ascending, offsets [B, V + 1].  grid (ceil(V / kPointsPerBlock), B)
+__global__ __launch_bounds__(kThreads) void k_ray_backward_vertices(
+    const V3 *__restrict__ directions, const V3 *__restrict__ vertices, const int32_t *__restrict__ triangles,
+    const int32_t *__restrict__ lengths, int N, int V, int T, const int32_t *__restrict__ face,
+    const V3 *__restrict__ bary, const int32_t *__restrict__ order, const int32_t *__restrict__ offsets,
+    const float *__restrict__ g_t, V3 *__restrict__ dvertices) {
+  const int b = (int)blockIdx.y;
+  const int nv = valid_count(lengths, b, N);
+  gather_rows(b, V, dvertices, [&](int v, int sub, float &dx, float &dy, float &dz) {
+    const int32_t *off = offsets + (size_t)b * (V + 1);
+    const int e0 = max(off[v], 0), e1 = min(off[v + 1], 3 * N);
+    for (int k = e0 + sub; k < e1; k += kLanesPerPoint) {
+      const int e = order[(size_t)b * 3 * N + k];
+      if ((unsigned)e >= (unsigned)(3 * N)) continue;
+      const int i = e / 3, corner = e - 3 * i;
+      V3 g;
+      if (!ray_gradient(vertices + (size_t)b * V, triangles, face + (size_t)b * N, directions + (size_t)b * N, i, nv,
+                        V, T, g))
+        continue;
+      const V3 w = bary[(size_t)b * N + i];
+      const float s = g_t[(size_t)b * N + i] * (corner == 0 ? w.x : (corner == 1 ? w.y : w.z));
+      dx += s * g.x;
+      dy += s * g.y;
+      dz += s * g.z;
+    }
+  });
 }
 
 // ---- launches ---------------------------------------------------------------------------------------------------
@@ -1415,12 +1746,50 @@ int launch_winding_number_forward(const float *points, const float *vertices, co
   const Plan p = wn_plan_of(B, N, T);
   const Workspace space = carve(ws, p, wn_layout(p, B, N, T), false);
   long long *partials = (long long *)space.keys;   // null without a split
-  int rc = launch(k_wn_setup, rows_grid(T, B), s, (const V3 *)vertices, triangles, V, T, space.records);
+  int rc = launch(k_wn_setup<false>, rows_grid(T, B), s, (const V3 *)vertices, triangles, V, T, space.records);
   if (rc != MR_OK) return rc;
   const auto sum = p.queries_per_lane == kTriWideQueries ? k_wn_sum<F2> : k_wn_sum<float>;
   rc = launch(sum, search_grid(p, B), s, points, (const float4 *)space.records, lengths, N, T, p.chunk, w, partials);
   if (rc == MR_OK && partials)
     rc = launch(k_wn_merge, rows_grid(N, B), s, (const long long *)partials, p.splits, lengths, N, w);
+  return rc;
+}
+
+// ray casting has the winding number's shape and workspace: the corner records | the splits' keys, one per ray
+void cast_rays_plan(int B, int N, int T, int *splits, int *queries_per_lane, int *triangle_tile, int *workgroup) {
+  winding_number_plan(B, N, T, splits, queries_per_lane, triangle_tile, workgroup);
+}
+
+size_t cast_rays_ws(int B, int N, int T) { return winding_number_ws(B, N, T); }
+
+int launch_cast_rays_forward(const float *origins, const float *directions, const float *vertices,
+                             const int32_t *triangles, const int32_t *lengths, int B, int N, int V, int T, float t_min,
+                             float t_max, float *t, int32_t *face, float *bary, void *ws, hipStream_t s) {
+  const Plan p = wn_plan_of(B, N, T);
+  const Workspace w = carve(ws, p, wn_layout(p, B, N, T), false);
+  int rc = launch(k_wn_setup<true>, rows_grid(T, B), s, (const V3 *)vertices, triangles, V, T, w.records);
+  if (rc != MR_OK) return rc;
+  const auto search = p.queries_per_lane == kTriWideQueries ? k_ray_search<F2> : k_ray_search<float>;
+  rc = launch(search, search_grid(p, B), s, origins, directions, (const float4 *)w.records, lengths, N, T, p.chunk,
+              t_min, t_max, face, w.keys);
+  if (rc == MR_OK && w.keys)
+    rc = launch(k_nearest_merge, rows_grid(N, B), s, w.keys, p.splits, lengths, nullptr, N, T, nullptr, face, nullptr);
+  if (rc != MR_OK) return rc;
+  return launch(k_ray_finish, rows_grid(N, B), s, (const V3 *)origins, (const V3 *)directions,
+                (const float4 *)w.records, lengths, N, T, t_min, t_max, t, face, (V3 *)bary);
+}
+
+int launch_cast_rays_backward(const float *directions, const float *vertices, const int32_t *triangles,
+                              const int32_t *lengths, int B, int N, int V, int T, const float *t, const int32_t *face,
+                              const float *bary, const int32_t *order, const int32_t *offsets, const float *grad_t,
+                              float *dorigins, float *ddirections, float *dvertices, hipStream_t s) {
+  int rc = MR_OK;
+  if (dorigins || ddirections)
+    rc = launch(k_ray_backward_rays, rows_grid(N, B), s, (const V3 *)directions, (const V3 *)vertices, triangles,
+                lengths, N, V, T, t, face, grad_t, (V3 *)dorigins, (V3 *)ddirections);
+  if (rc == MR_OK && dvertices)
+    rc = launch(k_ray_backward_vertices, groups_grid(V, B), s, (const V3 *)directions, (const V3 *)vertices, triangles,
+                lengths, N, V, T, face, (const V3 *)bary, order, offsets, grad_t, (V3 *)dvertices);
   return rc;
 }
 

@@ -12,7 +12,9 @@ file and the same split between the HIP and the torch path; triangle_nearest_poi
 other direction, every triangle against its nearest point, and point_mesh_face_distance is the sum of the two means.
 winding_number says on which side of the mesh a point lies -- the generalized winding number, an order-free fixed-point
 sum over all triangles with kernels of the same file -- inside_mesh thresholds it, and signed_distance puts its sign
-on nearest_triangles' distance.
+on nearest_triangles' distance.  cast_rays asks the sensor's question -- along this ray, where is the mesh first met? --
+with the watertight test of Woop, Benthin and Wald in kernels of the same file, differentiable in the rays and the
+vertices; rays_occluded is its yes or no.
 knn_points is the K-neighbour form of nearest_points (a sorted list of K keys per query in registers, same file, same
 split between the two paths), knn_gather reads values at its indices, and estimate_point_normals is its first
 consumer: the normals of a scan from the covariance of every point's neighbourhood.  sample_farthest_points thins a
@@ -955,6 +957,191 @@ def signed_distance(points, vertices, triangles, lengths=None, threshold=0.5):
     distance = torch.where(nonzero, torch.sqrt(torch.where(nonzero, sqdist, torch.ones_like(sqdist))),
                            torch.zeros_like(sqdist))
     return torch.where(inside, -distance, distance)
+
+
+# ---- ray casting: where a ray first meets the mesh ------------------------------------------------------------------------
+
+_RAY_MAX_TRIANGLES = 1 << 24   # the winding number's size limits (include/mesh_raster.h)
+
+
+def _pick(x, k):
+    """x [...,3], k [...] int64 -> x[..., k] [...]."""
+    return torch.gather(x, -1, k[..., None].expand(*x.shape[:-1], 1))[..., 0]
+
+
+def _cast_rays_torch(o, d, v, tris, lengths, t_min, t_max):
+    """cast_rays as a torch expression on the device and in the dtype of o, d [B,N,3] / v [B,V,3], chunked over the
+    rays, without a graph: the definition of include/mesh_raster.h operation by operation.  The fused multiply-add of
+    the shear is formed in float64 and rounded back (the product is exact there), the edge functions are two rounded
+    products and a rounded difference in the tensors' dtype and are recomputed in float64 where one is exactly 0.  The
+    shear is applied per VERTEX and gathered per triangle, so two triangles see the same numbers at a shared corner."""
+    B, N, _ = o.shape
+    V, T = v.shape[1], tris.shape[0]
+    dev, dtype = o.device, o.dtype
+    n_valid = lengths.long() if lengths is not None else torch.full((B,), N, dtype=torch.int64, device=dev)
+    with torch.no_grad():
+        o, d, v = o.detach(), d.detach(), v.detach()
+        safe = tris.clamp(0, V - 1)
+        finite = torch.isfinite(v).all(-1)                                                # [B,V]
+        usable = (((tris >= 0) & (tris < V)).all(dim=1) & (tris[:, 0] != tris[:, 1]) & (tris[:, 1] != tris[:, 2])
+                  & (tris[:, 2] != tris[:, 0]))[None] & finite[:, safe[:, 0]] & finite[:, safe[:, 1]] & finite[:, safe[:, 2]]
+        lo, hi = torch.tensor(t_min, dtype=dtype, device=dev), torch.tensor(t_max, dtype=dtype, device=dev)
+        inf = torch.tensor(float("inf"), dtype=dtype, device=dev)
+        rows = max(1, _CHUNK_BYTES // max(1, B * max(T, V) * 24 * 8))
+        ts, faces, barys = [], [], []
+        for start in range(0, N, rows):
+            oc, dc = o[:, start:start + rows], d[:, start:start + rows]
+            R = oc.shape[1]
+            size = dc.abs().max(-1).values
+            live = (torch.isfinite(oc).all(-1) & torch.isfinite(dc).all(-1) & (size > 0)
+                    & (torch.arange(start, start + R, device=dev)[None, :] < n_valid[:, None]))
+            oc = torch.where(live[..., None], oc, torch.zeros_like(oc))
+            dc = torch.where(live[..., None], dc, torch.ones_like(dc))
+            kz = (dc.abs() == dc.abs().max(-1, keepdim=True).values).to(torch.uint8).argmax(-1)   # the first that attains
+            kx, ky = (kz + 1) % 3, (kz + 2) % 3
+            dz = _pick(dc, kz)
+            kx, ky = torch.where(dz < 0, ky, kx), torch.where(dz < 0, kx, ky)
+            sx, sy, sz = _pick(dc, kx) / dz, _pick(dc, ky) / dz, 1.0 / dz
+            p = v[:, None] - oc[:, :, None]                                              # [B,R,V,3]
+            wide = lambda k: _pick(p, k[..., None].expand(B, R, V)).double()
+            pk = wide(kz)
+            px = (wide(kx) - sx.double()[..., None] * pk).to(dtype)                       # fma(-Sx, p[kz], p[kx])
+            py = (wide(ky) - sy.double()[..., None] * pk).to(dtype)
+            pz = sz[..., None] * pk.to(dtype)
+            ax, bx, cx = (px[:, :, safe[:, k]] for k in range(3))                         # [B,R,T]
+            ay, by, cy = (py[:, :, safe[:, k]] for k in range(3))
+            az, bz, cz = (pz[:, :, safe[:, k]] for k in range(3))
+            u, vv, w = cx * by - cy * bx, ax * cy - ay * cx, bx * ay - by * ax
+            zero = (u == 0) | (vv == 0) | (w == 0)
+            u64, v64, w64 = u.double(), vv.double(), w.double()
+            if bool(zero.any()):
+                ax, ay, bx, by, cx, cy = (x.double() for x in (ax, ay, bx, by, cx, cy))
+                u64 = torch.where(zero, cx * by - cy * bx, u64)
+                v64 = torch.where(zero, ax * cy - ay * cx, v64)
+                w64 = torch.where(zero, bx * ay - by * ax, w64)
+            mixed = ((u64 < 0) | (v64 < 0) | (w64 < 0)) & ((u64 > 0) | (v64 > 0) | (w64 > 0))
+            u, vv, w = u64.to(dtype), v64.to(dtype), w64.to(dtype)
+            det = (u + vv) + w
+            t = ((u * az + vv * bz) + w * cz) / det
+            accept = usable[:, None, :] & live[..., None] & ~mixed & (det != 0) & (t >= lo) & (t <= hi)
+            t = torch.where(accept, torch.where(t == 0, torch.zeros_like(t), t), inf)      # -0 is stored as +0
+            first = t.min(dim=2)                                                          # the first of equal minima
+            hit, index = first.values < inf, first.indices
+            at = lambda x: torch.gather(x, 2, index[..., None])[..., 0]
+            bary = torch.stack([at(u), at(vv), at(w)], -1) / torch.where(hit, at(det), torch.ones_like(first.values))[..., None]
+            ts.append(first.values)
+            faces.append(torch.where(hit, index, torch.full_like(index, -1)))
+            barys.append(torch.where(hit[..., None], bary, torch.zeros_like(bary)))
+        return torch.cat(ts, dim=1), torch.cat(faces, dim=1).to(torch.int32), torch.cat(barys, dim=1)
+
+
+def _ray_gradients_torch(d, v, tris, t, face, bary, grad, want=(True, True, True)):
+    """The analytic gradients of sum_i grad_i t_i with the face held fixed -> (dorigins, ddirections, dvertices), None
+    for what is not wanted: with n = (b - a) x (c - a) and g = n / (n . d), dt/do = -g, dt/dd = -t g, dt/dv_k =
+    bary_k g; 0 for a ray without a hit, with n . d == 0 or with a g that is not finite."""
+    V = v.shape[1]
+    hit = face >= 0
+    corner = tris.long().clamp(0, V - 1)[face.clamp(min=0).long()]                        # [B,N,3]
+    a, b, c = (torch.gather(v, 1, corner[..., k, None].expand(-1, -1, 3)) for k in range(3))
+    n = torch.cross(b - a, c - a, dim=-1)
+    s = (n * d).sum(-1)
+    ok = hit & (s != 0)
+    g = n / torch.where(ok, s, torch.ones_like(s))[..., None]
+    ok = ok & torch.isfinite(g).all(-1)
+    g = torch.where(ok[..., None], g, torch.zeros_like(g)) * torch.where(ok, grad, torch.zeros_like(grad))[..., None]
+    dorigins = -g if want[0] else None
+    ddirections = -g * torch.where(ok, t, torch.zeros_like(t))[..., None] if want[1] else None
+    dvertices = None
+    if want[2]:
+        dvertices = torch.zeros_like(v)
+        for k in range(3):
+            dvertices.scatter_add_(1, corner[..., k, None].expand(-1, -1, 3), bary[..., k, None] * g)
+    return dorigins, ddirections, dvertices
+
+
+class _CastRays(torch.autograd.Function):
+    """cast_rays on both routes: (t [B,N], face [B,N], bary [B,N,3]); the backward holds the face fixed and computes
+    only the gradients that are required."""
+
+    @staticmethod
+    def forward(ctx, origins, directions, vertices, triangles, lengths, t_min, t_max):
+        od, dd, vd = origins.detach().contiguous(), directions.detach().contiguous(), vertices.detach().contiguous()
+        ctx.hip = _on_hip_path(od)
+        if ctx.hip:
+            triangles = _device_triangles(triangles, vd.shape[1])
+            t, face, bary = _native.cast_rays_forward(od, dd, vd, triangles, lengths, t_min, t_max)
+        else:
+            t, face, bary = _cast_rays_torch(od, dd, vd, triangles, lengths, t_min, t_max)
+        ctx.save_for_backward(dd, vd, triangles, lengths, t, face, bary)
+        ctx.mark_non_differentiable(face, bary)
+        return t, face, bary
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad, _face=None, _bary=None):
+        directions, vertices, triangles, lengths, t, face, bary = ctx.saved_tensors
+        want = tuple(ctx.needs_input_grad[:3])
+        none = (None,) * 4
+        if not any(want):
+            return (None, None, None) + none
+        grad = grad.contiguous()
+        if not ctx.hip:
+            return _ray_gradients_torch(directions, vertices, triangles, t, face, bary, grad, want) + none
+        index = None
+        if want[2]:   # the (ray, corner) entries keyed by the vertex they name, -1 for rays without a hit
+            named = triangles[face.clamp(min=0).long()]                                  # [B,N,3]
+            named = torch.where(face[..., None] < 0, torch.full_like(named, -1), named)
+            index = _native.nearest_inverted_index(named.reshape(face.shape[0], -1), vertices.shape[1])
+        return _native.cast_rays_backward(directions, vertices, triangles, lengths, t, face, bary, grad, index,
+                                          want_dorigins=want[0], want_ddirections=want[1], want_dvertices=want[2]) + none
+
+
+def cast_rays(origins, directions, vertices, triangles, lengths=None, t_min=0.0, t_max=float("inf")):
+    """origins, directions [B,N,3], vertices [B,V,3] (or [N,3], [V,3]: one image, results without the batch axis),
+    triangles [T,3] of any integer dtype (one topology for the batch, at most 2^24 triangles) -> (t [B,N], face [B,N]
+    int32, bary [B,N,3]): where every ray first meets the mesh.  Directions are NOT normalised: t is in units of |d|
+    and the hit point is origins + t[..., None] * directions; bary are the hit point's barycentrics on the face.
+
+    The test is the watertight one of Woop, Benthin and Wald (2013), stated operation by operation in
+    include/mesh_raster.h and INTEGRATION.md ("Point-cloud losses"): a ray aimed at a shared edge or a vertex of a
+    closed mesh cannot slip between two triangles.  The first hit is the accepted triangle with the least t in
+    [t_min, t_max] (Python floats, 0 <= t_min <= t_max, rounded to the tensors' dtype); equal t goes to the lowest
+    face.  There is no back-face culling.  A triangle with an index outside [0, V), two equal indices or a corner that
+    is not finite is never hit.
+
+    A ray without a hit -- a padded row (lengths: an optional integer [B] tensor on the rays' device), a non-finite
+    origin or direction, a zero direction, nothing in [t_min, t_max] -- gets t = +inf, face = -1, bary = 0 and no
+    gradient.  t is differentiable in origins, directions and vertices with the face held fixed: with n = (b - a) x
+    (c - a) and g = n / (n . d), dt/do = -g, dt/dd = -t g, dt/dv_k = bary_k g, and 0 (never NaN) where n . d is 0 or g
+    is not finite; a gradient that is not required is not computed.  face and bary are not differentiable.
+
+    On a HIP device with float32 tensors the search runs in csrc/nearest.hip (k_ray_*): t, face and bary of a ray are
+    the same bit for bit whatever the batch it sits in.  Host tensors and tensors that are not float32 take the torch
+    expression of the same definition."""
+    p, v, tris, lengths, single = _point_mesh_arguments(origins, vertices, triangles, lengths)
+    _cloud("directions", directions)
+    if directions.shape != origins.shape:
+        raise ValueError("origins and directions must have the same shape, got %s and %s"
+                         % (list(origins.shape), list(directions.shape)))
+    if directions.device != p.device:
+        raise RuntimeError("origins and directions must be on the same device")
+    if directions.dtype != p.dtype:
+        raise RuntimeError("origins and directions must have the same dtype, got %s and %s" % (p.dtype, directions.dtype))
+    if isinstance(t_min, bool) or isinstance(t_max, bool) or not all(isinstance(x, (int, float)) for x in (t_min, t_max)):
+        raise ValueError("t_min and t_max must be Python floats, got %r and %r" % (t_min, t_max))
+    if not 0.0 <= t_min <= t_max:
+        raise ValueError("0 <= t_min <= t_max is required, got %r and %r" % (t_min, t_max))
+    if tris.shape[0] > _RAY_MAX_TRIANGLES:
+        raise ValueError("cast_rays takes at most 2^24 triangles, got %d" % tris.shape[0])
+    d = directions.unsqueeze(0) if single else directions
+    out = _CastRays.apply(p, d, v, tris, lengths, float(t_min), float(t_max))
+    return tuple(x[0] for x in out) if single else tuple(out)
+
+
+def rays_occluded(origins, directions, vertices, triangles, lengths=None, t_min=0.0, t_max=float("inf")):
+    """cast_rays(...)[1] >= 0 -> bool [B,N]: whether the mesh meets the ray within [t_min, t_max].  With the direction
+    q - p and t_max = 1 it is the line of sight from p to q."""
+    return cast_rays(origins, directions, vertices, triangles, lengths, t_min, t_max)[1] >= 0
 
 
 # ---- registration: the similarity transform between matched points, and ICP ---------------------------------------------
